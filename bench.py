@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- DDPG gradient updates/sec/GPU on synthetic Pendulum-shaped replay (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--agents A] [--updates-per-step U]
+    python bench.py --gpus N --steps K --warmup W [--agents A] [--updates-per-step U] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the result line.  --full adds
+the CPU baseline and the SAC / NAF / ReverseKL / separate-network DDPG sub-records (see below), each a measurement of
+its own.  --dump-outputs DIR writes what the timed path computed in its last step (dump_outputs()); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload: obs 3, act 1, shared/actor/critic layers 200/200/200,
 batch 100, actor_lr 1e-3, critic_lr 1e-2, tau 0.01; every agent owns a device-resident replay of 1e6
@@ -20,9 +25,9 @@ The JSON line also carries
   roofline      dominant kernel vs the fp32 matrix-core peak (the binding roof: 27.8 FLOP/B algorithmic
                 intensity > 19.7 ridge), achieved = 73.2 MFLOP x updates per launch / HIP-event launch time
   roofline_hbm  the same launch priced in algorithmic HBM bytes (2,634,064 B per update) vs 8 TB/s
-  cpu_baseline  the reference-structured CPU port (oracle/) timed on this host, rank 0 at N=1 only
-  ddpg_separate (N=1 only) the `network: separate` variant of DDPG on the MFMA kernel
-  sac, naf      (N=1 only) the same measurement for BASELINE configs[2] / [3]: SoftActorCritic (S=3 A=1 L=128) and
+  cpu_baseline  (--full) the reference-structured CPU port (oracle/) timed on this host, rank 0 at N=1 only
+  ddpg_separate (--full, N=1 only) the `network: separate` variant of DDPG on the MFMA kernel
+  sac, naf      (--full, N=1 only) the same measurement for BASELINE configs[2] / [3]: SoftActorCritic (S=3 A=1 L=128) and
                 NAF (S=8 A=2 L=200) fused update kernels, 256 agents x 1e6-record replays, each with its own
                 flop_per_update and roofline fraction; the DDPG headline stays `value`
 """
@@ -214,6 +219,38 @@ def aggregate_value(world, agents, updates_per_step, steps, dt_max):
     return world * agents * updates_per_step * steps / dt_max
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_PARAM_AGENTS = 32            # agents whose full parameter vectors are written (all of them would be 84 MB at A=256)
+
+
+def dump_outputs(pop, out_dir, seed=0):
+    """What a caller of the timed path receives after its last step, as <out_dir>/<name>.npy (float32):
+      q, y, a_out, dqda       [agents, batch(, action)] the last update's taps of EVERY agent (Q(s,a), TD target,
+                              mu(s), dQ/da on that update's minibatch)
+      theta, theta_target     [k, P] the parameters and target parameters of a fixed sample of k agents
+      sample_agents           [k] which agents those are (RandomState(seed) choice, sorted; the same for the same --agents)
+      beta_powers             [agents, 4] the Adam beta powers (actor beta1, beta2, critic beta1, beta2)
+    Returns {name: shape}.  The whole is kept under 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    NA = pop.n_agents
+    k = min(NA, DUMP_PARAM_AGENTS)
+    sample = np.sort(np.random.RandomState(seed).choice(NA, k, replace=False))
+    out = {}
+    for name in ("q", "y", "a_out", "dqda"):
+        shape = (NA, pop.B, pop.A) if name in ("a_out", "dqda") else (NA, pop.B)
+        out[name] = np.stack([pop.last_tap(i, name) for i in range(NA)]).reshape(shape)
+    out["theta"] = np.stack([pop.get_blob(i, "theta") for i in sample])
+    out["theta_target"] = np.stack([pop.get_blob(i, "theta_target") for i in sample])
+    out["sample_agents"] = sample.astype(np.float32)
+    out["beta_powers"] = np.stack([pop.get_beta_powers(i) for i in range(NA)])
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_LIMIT_BYTES))
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, np.float32))
+    return {name: v.shape for name, v in out.items()}
+
+
 def measured_peaks():
     """roofs measured on a box of this pool by scripts/micro/peaks.hip (profiles/r03_peaks.json): quoted beside the spec
     peaks the fractions are priced against; None when the file is absent"""
@@ -327,8 +364,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group at world size 1 too (one rank under torch.distributed.run): barrier, "
                          "MAX all-reduce and all-gather then go through RCCL -- the one-GPU rehearsal of --gpus 8")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-records", action="store_true", help="skip the SAC / NAF sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and the SAC / NAF / ReverseKL / separate-network DDPG sub-records "
+                         "(a plain run measures the DDPG headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs; "
+                         "rank 0's agents when N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side-records", action="store_true", help="with --full: skip the SAC / NAF sub-records")
     ap.add_argument("--side-only", default="", choices=["", "sac", "naf", "kl", "ddpg_separate"],
                     help="profiling helper: run ONLY that sub-record (no DDPG headline) and print its JSON")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -343,7 +386,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_base = None
-    if rank == 0 and world_env == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_env == 1 and not args.no_cpu_baseline:
         from __graft_entry__ import build_oracle
         build_oracle()
         cpu_base = cpu_baseline(args.cpu_seconds, args.cpu_records)   # before the GPU is initialised (child processes)
@@ -396,6 +439,8 @@ def main():
     dt, ev_ms = measure(pop, U, args.steps, args.warmup, dist, torch.cuda.synchronize)
     red_dev = "cuda" if (dist is None or args.backend == "nccl") else "cpu"
     dt_max, gathered = reduce_over_ranks(dt, float(np.mean(pop.last_tap(0, "q"))), dist, world, red_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pop, args.dump_outputs)
     pop.close()
 
     if rank == 0:
@@ -430,8 +475,9 @@ def main():
         if dist is not None:
             out["config"]["collectives"] = "%s: barrier x2, all_reduce(MAX) x1, all_gather x1 over %d rank(s)" % (
                 dist.get_backend(), world)
+        out["full"] = args.full
         out["cpu_baseline"] = cpu_base
-        if world == 1 and not args.no_side_records:
+        if args.full and world == 1 and not args.no_side_records:
             # BASELINE configs[2], [3] on the same box, same agent count and replay size (extra keys; `value` is DDPG)
             # the same launch length as the headline: U x steps = 6,400 timed updates per agent by default
             for algo in ("sac", "naf", "kl", "ddpg_separate"):

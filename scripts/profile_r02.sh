@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r02_prof
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- python3 bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- python3 bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
 SHORT="--no-cpu-baseline --no-side-records --steps 4 --warmup 1 --updates-per-step 32"
 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- python3 bench.py $SHORT > $OUT/fetch.json 2> $OUT/fetch.err || exit 1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o write -- python3 bench.py $SHORT > $OUT/write.json 2> $OUT/write.err || exit 1

@@ -6,9 +6,9 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r03_prof
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- python3 bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- python3 bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
 python scripts/rocpd_extract.py --db $(find $OUT/stats -name "*_results.db" | head -1) --stats --out $OUT/r03_bench_default || exit 1
-python bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err || exit 1
+python bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err || exit 1
 python -c "
 import json
 d = json.loads(open('$OUT/bench_plain.json').read().strip().splitlines()[-1])

@@ -261,7 +261,10 @@ def main():
         json.dump(rms_state(), f, indent=1)
     ck = bimodal_ckpt()
     np.savez_compressed(os.path.join(HERE, "bimodal_uneq_var1_qf.npz"), **ck)
-    np.savez_compressed(os.path.join(HERE, "bimodal_qf_ckpts.npz"), **bimodal_ckpts_all())
+    ckpts = bimodal_ckpts_all()
+    for name in BIMODAL_REWARDS:        # one file per checkpoint: each stays well under the 1 MiB a committed file may hold
+        np.savez_compressed(os.path.join(HERE, "bimodal_qf_ckpt_%s.npz" % name),
+                            **{k: v for k, v in ckpts.items() if k.split("/")[0] == name})
     print("golden vectors written to", HERE)
 
 

@@ -1,6 +1,6 @@
 """Pins taken from the ONLY network-side artefacts the reference holds: the five Bimodal1DEnv_trueQ_ckpt checkpoints
 (SAC `main/qf` critics trained for 10 000 Adam steps by TF-1.15; agents/SoftActorCritic.py:37-49 loads them).
-tests/golden/make_golden.py parses them weights-only into bimodal_qf_ckpts.npz.
+tests/golden/make_golden.py parses them weights-only into bimodal_qf_ckpt_<name>.npz, one file per checkpoint.
 
 What they pin:
   * the optimizer's beta2 power is the fp32 RUNNING PRODUCT p <- p * 0.999f (TF keeps beta powers as fp32 variables
@@ -22,7 +22,12 @@ STEPS = 10000
 
 @pytest.fixture(scope="module")
 def ck(golden_dir):
-    return np.load(os.path.join(golden_dir, "bimodal_qf_ckpts.npz"))
+    """{"<checkpoint>/<tensor>": array} of all five checkpoints (one file each: tests/golden/bimodal_qf_ckpt_*.npz)"""
+    out = {}
+    for name in NAMES:
+        with np.load(os.path.join(golden_dir, "bimodal_qf_ckpt_%s.npz" % name)) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 FLT_MIN = np.float32(1.17549435e-38)
