@@ -365,9 +365,20 @@ int rlc_naf_get_kernel(const rlc_naf* h, int32_t* variant_in_use);
  * mid-episode: quirk Q8).  Evaluation 0 runs before the first training step.  Random streams (environment
  * resets, OU normals, minibatch indices) are Philox streams keyed by the agent's seed.
  * ------------------------------------------------------------------------------------------------- */
-#define RLC_ENV_PENDULUM_V0 1          /* gym 0.18 Pendulum-v0 (third-party; restated, float64 simulator) */
+#define RLC_ENV_PENDULUM_V0 1          /* gym 0.18 Pendulum-v0 (third-party; restated, float64 simulator); S 3, A 1 */
+/* The reference's toy environments (environments/environments.py:158-912), float64, pinned to the reference by
+ * tests/golden/bimodal_envs.json.  The seven one-step bandits are consecutive ids (one device function, a constant
+ * table): S 1, A 1, every transition stored with gamma 0.  Bimodal2DEnv: S 2, A 2, reports `done` at the goals. */
+#define RLC_ENV_BIMODAL1D 2            /* Bimodal1DEnv */
+#define RLC_ENV_BIMODAL1D_UNEQ_VAR1 3
+#define RLC_ENV_BIMODAL1D_UNEQ_VAR2 4
+#define RLC_ENV_BIMODAL1D_UNEQ_VAR3 5
+#define RLC_ENV_BIMODAL1D_EQ_VAR1 6
+#define RLC_ENV_BIMODAL1D_EQ_VAR2 7
+#define RLC_ENV_BIMODAL1D_EQ_VAR3 8
+#define RLC_ENV_BIMODAL2D 9            /* Bimodal2DEnv */
 typedef struct rlc_rollout_config {
-    int32_t env_id;                    /* RLC_ENV_PENDULUM_V0 */
+    int32_t env_id;                    /* one of RLC_ENV_* */
     int32_t episode_steps_limit;       /* EPISODE_STEPS_LIMIT (environments/environments.py:40-46) */
     int64_t total_steps_limit;         /* TOTAL_STEPS_LIMIT */
     int64_t eval_interval;             /* training steps between evaluations (>= 1) */

@@ -12,8 +12,8 @@ offline tooling reads identical fields).  Differences: no TensorFlow summary wri
 and ``--gpu`` picks the HIP device.
 
 ``--device_rollout`` runs ALL indices of the range concurrently as one population on the GPU with the
-environment simulated on the device (rlcontrol_amd/device_experiment.py; DDPG, SoftActorCritic or NAF on Pendulum-v0):
-same schedule, same pickle, Philox random streams instead of numpy's.
+environment simulated on the device (rlcontrol_amd/device_experiment.py; the five agents on Pendulum-v0 or on one
+of the Bimodal toy environments): same schedule, same pickle, Philox random streams instead of numpy's.
 
 Under ``python -m torch.distributed.run --nproc-per-node N main.py ...`` the INDEX range is dealt round-robin to
 the N ranks (one GPU each, nothing exchanged while training); one all-gather of the run records at the end
@@ -176,8 +176,10 @@ def _make_population(agent_name, members, arg_params):
     return pop
 
 
-def run_indices_on_device(indices, agent_json, env_json, env_params, arg_params, data, verbose=True, progress=None):
-    """All `indices` at once: one population per group of indices that share the network / replay shape."""
+def run_indices_on_device(indices, agent_json, env_json, env_params, arg_params, data, verbose=True, progress=None,
+                          inspect=None):
+    """All `indices` at once: one population per group of indices that share the network / replay shape.
+    `inspect(indices_of_the_group, population)` is called after a group's run, before its population is closed."""
     from rlcontrol_amd.device_experiment import DeviceExperiment
     agent_name = agent_json['agent']
     if agent_name not in _SHARED_KEYS:
@@ -203,6 +205,8 @@ def run_indices_on_device(indices, agent_json, env_json, env_params, arg_params,
         results = exp.run(progress=progress)
         for m, res in zip(members, results):
             out[m[0]] = (m[1], m[2], _run_data(m[3].random_seed, env_json, res))
+        if inspect is not None:
+            inspect([m[0] for m in members], pop)
         pop.close()
     for index in indices:            # pickle layout: runs appended in index order, as the sequential driver does
         sweep, agent_params, run_data = out[index]

@@ -114,7 +114,11 @@ class rlc_rollout_config(ctypes.Structure):
     ]
 
 
-ENV_IDS = {"Pendulum-v0": 1}
+# RLC_ENV_* of include/rlcontrol_hip.h, and the EPISODE_STEPS_LIMIT an env json with "EpisodeSteps": -1 means
+ENV_IDS = {"Pendulum-v0": 1, "Bimodal1DEnv": 2, "Bimodal1DEnv_uneq_var1": 3, "Bimodal1DEnv_uneq_var2": 4,
+           "Bimodal1DEnv_uneq_var3": 5, "Bimodal1DEnv_eq_var1": 6, "Bimodal1DEnv_eq_var2": 7, "Bimodal1DEnv_eq_var3": 8,
+           "Bimodal2DEnv": 9}
+ENV_DEFAULT_EPISODE_STEPS = dict({name: 1 for name in ENV_IDS}, **{"Pendulum-v0": 200})
 
 
 _lib = None

@@ -39,7 +39,10 @@ __device__ __noinline__ int rlc_train_step_device(const RlcRollout* ro, int agen
     const int fresh = env.need_reset[agent];
     if (fresh) {
         // run_episode_train: env.reset(); agent.reset()  (experiment.py:103-107)
-        if (tid == 0) rlc_env_begin_episode(dv.rep, env, agent);
+        if (tid == 0) {
+            if (fresh == 2) dv.noise_ctr[agent] += 1;      // the discarded agent.step() at the step limit
+            rlc_env_begin_episode(dv.rep, env, agent);
+        }
         if (tid < A) dv.ou_state[agent * A + tid] = dv.ou_mu;
         __syncthreads();
     }

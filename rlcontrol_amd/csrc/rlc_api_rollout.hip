@@ -25,14 +25,18 @@ extern "C" {
 static int rollout_alloc(rlc_handle* h, const rlc_rollout_config* cfg) {
     RLC_REQUIRE(!h->has_env, "rollout already configured on this handle");
     if (rlc_h_use_device(h)) return 1;
-    RLC_REQUIRE(cfg->env_id == RLC_ENV_PENDULUM_V0, "unknown env_id %d (built in: RLC_ENV_PENDULUM_V0)", cfg->env_id);
-    RLC_REQUIRE(h->rep.S == 3 && h->rep.A == 1, "Pendulum-v0 needs state_dim 3 / action_dim 1 (handle has %d / %d)",
-                h->rep.S, h->rep.A);
+    RLC_REQUIRE(cfg->env_id >= RLC_ENV_PENDULUM_V0 && cfg->env_id <= RLC_ENV_BIMODAL2D,
+                "unknown env_id %d (built in: RLC_ENV_PENDULUM_V0, RLC_ENV_BIMODAL1D* and RLC_ENV_BIMODAL2D)", cfg->env_id);
+    const bool pend = cfg->env_id == RLC_ENV_PENDULUM_V0, two_d = cfg->env_id == RLC_ENV_BIMODAL2D;
+    const char* env_name = pend ? "Pendulum-v0" : two_d ? "Bimodal2DEnv" : "the Bimodal1DEnv family";
+    const int need_s = pend ? 3 : two_d ? 2 : 1, need_a = two_d ? 2 : 1;
+    RLC_REQUIRE(h->rep.S == need_s && h->rep.A == need_a, "%s needs state_dim %d / action_dim %d (handle has %d / %d)",
+                env_name, need_s, need_a, h->rep.S, h->rep.A);
     RLC_REQUIRE(cfg->episode_steps_limit >= 1 && cfg->total_steps_limit >= 0 && cfg->eval_interval >= 1 &&
                 cfg->eval_episodes >= 0 && cfg->warmup_steps >= 0 && cfg->max_train_episodes >= 1,
                 "bad rollout configuration");
     RlcEnvDev& e = h->env;
-    e.env_id = RLC_ENV_PENDULUM;
+    e.env_id = cfg->env_id;
     e.episode_limit = cfg->episode_steps_limit;
     e.learn_threshold = cfg->warmup_steps > h->B ? cfg->warmup_steps : h->B;
     e.eval_episodes = cfg->eval_episodes;

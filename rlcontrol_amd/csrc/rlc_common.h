@@ -219,7 +219,8 @@ struct RlcEnvDev {
     double* obs;                         // [n_agents][S] current observation of the training episode
     int* ep_step;                        // [n_agents]
     double* ep_ret;                      // [n_agents]
-    int* need_reset;                     // [n_agents] 1 = next train step starts a new episode
+    int* need_reset;                     // [n_agents] != 0: next train step starts a new episode; 2 = the last one ended
+                                         // at the step limit without `done` (one exploration draw is skipped)
     long long* total_steps;              // [n_agents]
     unsigned long long* reset_ctr;       // [n_agents] training-environment resets so far
     double* train_ret; int* train_len; long long* train_cum; int* n_train_ep;   // [n_agents][max_episodes], [n_agents]

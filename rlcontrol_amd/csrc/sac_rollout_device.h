@@ -28,8 +28,12 @@ __device__ __noinline__ int rlc_sac_train_step_device(const RlcSacRollout* ro, i
     double* obs = env.obs + (size_t)agent * S;
 
     __syncthreads();
-    if (env.need_reset[agent]) {
-        if (tid == 0) rlc_env_begin_episode(dv.rep, env, agent);
+    const int fresh = env.need_reset[agent];
+    if (fresh) {
+        if (tid == 0) {
+            if (fresh == 2) dv.noise_ctr[agent] += 1;      // the discarded agent.step() at the step limit
+            rlc_env_begin_episode(dv.rep, env, agent);
+        }
         __syncthreads();
     }
     for (int i = tid; i < S; i += nthr) L.x[i] = rlc_clip_scalar((float)obs[i], dv.clip_state, dv.smin0, dv.smax0);

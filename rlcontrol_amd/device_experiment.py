@@ -3,8 +3,9 @@
 ``DeviceExperiment(population, env_params, gamma, warmup_steps)`` drives the C ABI's rollout block
 (include/rlcontrol_hip.h): every agent of a ``DDPGPopulation`` (act + OU noise), ``SACPopulation``
 (reparameterised sample of the policy) or ``NAFPopulation`` (draw from N(mu, noise_scale (L L^T)^-1)) runs its
-own train / evaluate loop on the device -- act, Pendulum step,
-replay insert, gated fused update, periodic greedy evaluation -- with no host round trip per step.  ``run()`` returns, per agent, the reference's 9-tuple
+own train / evaluate loop on the device -- act, environment step (Pendulum-v0 or one of the reference's Bimodal toy
+environments, ``_lib.ENV_IDS``), replay insert, gated fused update, periodic greedy evaluation -- with no host
+round trip per step.  ``run()`` returns, per agent, the reference's 9-tuple
 (train_rewards_per_episode, eval_rewards_per_episode, train_steps_per_episode, eval_steps_per_episode,
 timesteps_at_eval, cum_train_time, cum_eval_time, train_episodes, train_cum_steps).
 
@@ -33,7 +34,8 @@ class DeviceExperiment(object):
         self.total_steps_limit = int(env_params['TotalMilSteps'] * 1000000)
         self.eval_interval = int(env_params['EvalIntervalMilSteps'] * 1000000)
         self.eval_episodes = int(env_params['EvalEpisodes'])
-        self.episode_steps_limit = 200 if env_params['EpisodeSteps'] == -1 else int(env_params['EpisodeSteps'])
+        self.episode_steps_limit = (_lib.ENV_DEFAULT_EPISODE_STEPS[name] if env_params['EpisodeSteps'] == -1
+                                    else int(env_params['EpisodeSteps']))
         if max_train_episodes is None:
             max_train_episodes = max(1, min(self.total_steps_limit, 1 << 20))
         cfg = _lib.rlc_rollout_config()

@@ -2,13 +2,14 @@
 
 ``create_environment(env_json)`` returns an object with the attributes Experiment and main.py read:
 ``name, eval_interval, eval_episodes, TOTAL_STEPS_LIMIT, EPISODE_STEPS_LIMIT, state_dim/min/max,
-action_dim/min/max`` and ``set_random_seed / reset / step / close``.  Pendulum-v0 is served by the
-in-tree restatement (gym is absent here); any other name is looked up in an installed ``gym`` and
-fails loudly when there is none.  The reference's Bimodal toy environments are out of scope
-(SURVEY.md section 2, row 14).
+action_dim/min/max`` and ``set_random_seed / reset / step / close``.  The reference's eight toy environments
+(``Bimodal1DEnv``, its six variants and ``Bimodal2DEnv``) are dispatched by name to ``bimodal.py``, as the
+reference does (environments.py:16-37).  Pendulum-v0 is served by the in-tree restatement (gym is absent here);
+any other name is looked up in an installed ``gym`` and fails loudly when there is none.
 """
 import numpy as np
 
+from . import bimodal
 from .pendulum import PendulumEnv
 
 
@@ -18,11 +19,14 @@ def _make_instance(name):
     try:
         import gym  # noqa: F401
     except ImportError:
-        raise RuntimeError("environment %r needs gym, which is not installed; only Pendulum-v0 is built in" % name)
+        raise RuntimeError("environment %r needs gym, which is not installed; built in: Pendulum-v0, %s"
+                           % (name, ", ".join(bimodal.NAMES)))
     return gym.make(name)
 
 
 def create_environment(env_params):
+    if env_params['environment'] in bimodal.NAMES:
+        return bimodal.create(env_params)
     return ContinuousEnvironment(env_params)
 
 
