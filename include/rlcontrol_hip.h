@@ -241,7 +241,8 @@ int rlc_sac_get_kernel(const rlc_sac* h, int32_t* variant_in_use);
  * action_dim 1 .. 6.  The caller supplies the nodes and weights of the action integral: the Clenshaw-Curtis line rule for
  * one action dimension (reversekl_network.py:64-76), the sparse grid of level l_param above it (:78-108).  Above one
  * dimension the policy is the reference's MultivariateNormal(mean, diag_embed(std)) -- covariance diag(std), i.e. a
- * variance of std per component (:383-389) -- reproduced as written; the MFMA kernel covers action_dim 1 only. */
+ * variance of std per component (:383-389) -- reproduced as written.  The MFMA kernel covers action_dim 1 (where it is
+ * the default) and action_dim 2 (on request: rlc_kl_set_kernel; a new population runs the any-shape kernel there). */
 #define RLC_KL_REVERSE 1
 #define RLC_KL_FORWARD 2
 #define RLC_KL_OPTIM_INTG 0        /* config.optim_type 'intg'      (reverse: soft RKL; forward: the only one implemented there) */
@@ -297,13 +298,15 @@ int rlc_kl_update_batch(rlc_kl* h, int32_t agent, int32_t batch, const double* s
  * the integral updates only) */
 int rlc_kl_last_tap(rlc_kl* h, int32_t agent, int32_t which, float* dst, int64_t n);
 int rlc_kl_enable_grad_taps(rlc_kl* h, int32_t on);
-/* kernel selection, as rlc_sac_set_kernel: 0 auto, 1 generic, 2 MFMA (state_dim <= 7, widths multiples of 4 in
- * [16,256], batch_size <= 32, at most 256 nodes, LDS permitting) */
+/* kernel selection, as rlc_sac_set_kernel: 0 auto, 1 generic, 2 MFMA (action_dim 1 or 2, state_dim + action_dim <= 8,
+ * widths multiples of 4 in [16,256], batch_size <= 128, at most 256 nodes, LDS <= 160 KiB; a refusal names the limit).
+ * 0 chooses the MFMA kernel at action_dim 1 only: at action_dim 2 it runs on request (2). */
 int rlc_kl_set_kernel(rlc_kl* h, int32_t variant);
 int rlc_kl_get_kernel(const rlc_kl* h, int32_t* variant_in_use);
 /* latency mode, as rlc_ddpg_set_split: n_workgroups (1..8) CUs per agent.  The forward passes of Q at the (state, node)
  * pairs of the action integral -- two thirds of an update -- are dealt over them; results are bit-identical to the
- * one-workgroup kernel's.  MFMA kernel and the integral updates only; host loop only; the GPU must not be shared. */
+ * one-workgroup kernel's.  MFMA kernel, action_dim 1, batch_size <= 32 and the integral updates only; host loop only;
+ * the GPU must not be shared. */
 int rlc_kl_set_split(rlc_kl* h, int32_t n_workgroups);
 
 

@@ -92,7 +92,7 @@ _SHARED_KEYS = {
             "exploration_policy"),
     "ReverseKL": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size", "tau",
                   "gamma", "warmup_steps", "exploration_policy", "sample_for_eval", "N_param", "l_param", "optim_type",
-                  "q_update_type", "use_true_q"),
+                  "q_update_type", "use_true_q", "hip_kernel"),
 }
 _SHARED_KEYS["ForwardKL"] = _SHARED_KEYS["ReverseKL"]
 
@@ -124,6 +124,12 @@ def _make_population(agent_name, members, arg_params):
         for i, m in enumerate(members):
             pop.set_params(i, init_params(c0.state_dim, c0.action_dim, c0.actor_l1_dim, c0.actor_l2_dim, c0.critic_l1_dim,
                                           c0.critic_l2_dim, m[3].random_seed), init_target=True)
+        # optional json key "hip_kernel" as in agents/ReverseKL.py ("mfma" is the only way to that kernel at action_dim 2)
+        kernel = getattr(c0, "hip_kernel", "auto")
+        if kernel not in KLPopulation.KERNEL:
+            raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(KLPopulation.KERNEL)))
+        if kernel != "auto":
+            pop.set_kernel(kernel)
         return pop
     check_norm_type(c0, agent_name + " --device_rollout",
                     ('input_norm', 'layer') if agent_name == "SoftActorCritic" else ('none', 'input_norm', 'layer'))

@@ -42,6 +42,13 @@ class KL_Network_Manager(BaseNetwork_Manager):
         theta0 = init_params(config.state_dim, config.action_dim, config.actor_l1_dim, config.actor_l2_dim,
                              config.critic_l1_dim, config.critic_l2_dim, config.random_seed)
         self.population.set_params(0, theta0, init_target=True)
+        # optional json key "hip_kernel": "auto" (the MFMA kernel where it is the default: action_dim 1), "generic" or
+        # "mfma" (the only way to it at action_dim 2; a shape it does not take fails with the library's message)
+        kernel = getattr(config, "hip_kernel", "auto")
+        if kernel not in KLPopulation.KERNEL:
+            raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(KLPopulation.KERNEL)))
+        if kernel != "auto":
+            self.population.set_kernel(kernel)
         # optional json key "hip_split": latency mode, this one agent's action integral over that many CUs (the GPU must
         # not be shared while it learns; rlc_kl_set_split)
         split = int(getattr(config, "hip_split", 1))

@@ -4,11 +4,12 @@
 // sample_batch + update_network + update_target_network of agents/ReverseKL.py:83-93 / agents/ForwardKL.py), built from
 // the MFMA blocks of mfma_blocks.h.  The three small networks are SoftActorCritic's family (sac_mfma_kernel.h) with
 // Q's action as one more INPUT column of its first layer (reversekl_network.py:257-276: xq = [s | a] goes through the
-// same first-layer block as a state of dimension S+1), torch's Adam (Blk<..., TADAM>), and a target for V only.
+// same first-layer block as a state of dimension S+A), torch's Adam (Blk<..., TADAM>), and a target for V only.
 // What is particular to these agents is the action integral: Q at the B x K (state, node) pairs,
 //     [B*K, L1c] x [L1c, L2c]   (1984 x 200 x 200 for the shipped jsons: 87 % of the update's flops),
 // runs as ceil(B*K / 16 MTQ) passes of the forward GEMM block at MTQ batch tiles: per pass the rows
-// relu(z1s[b] + a_k * W1[action row]) -- the first layer is separable, z1s = s W1[:S] + b1 is formed once per state --
+// relu(z1s[b] + sum_j a_kj * W1[action row j]) -- the first layer is separable, z1s = s W1[:S] + b1 is formed once per
+// state --
 // are GENERATED into the LDS activation image, the GEMM streams qW2 from L2, and bias / relu / the qW3 head fold into
 // its epilogue; only the B*K head values leave the CU (a global scratch row, 8 KB).
 //
@@ -18,7 +19,14 @@
 // Everything reads the PRE-update weights until its own network is stepped (the reference builds the three losses
 // before the first optimizer.step(), reversekl_network.py:139-218).
 //
-// Supported: action_dim 1, S <= 7, widths multiples of 4 in [16, 256], B <= 32, K <= 256 nodes, LDS <= 160 KiB.
+//
+// AD = action_dim, 1 or 2.  Above one dimension the policy is the reference's MultivariateNormal(mean, diag_embed(std))
+// (reversekl_network.py:383-389): component j has VARIANCE std_j, so the draw is mean + sqrt(std) eps, the log-density
+// sums -(z - mean)^2 / (2 std) - log sqrt(std) over the components and d / d log_std = delta^2 / (2 std) - 1/2
+// (kl_generic.hip states the same).  The AD = 1 instantiations keep Normal(mean, std): variance std^2.
+//
+// Supported: action_dim 1 or 2, S + action_dim <= 8, widths multiples of 4 in [16, 256], B <= 128, K <= 256 nodes,
+// LDS <= 160 KiB; latency mode (SPLIT) at action_dim 1 and B <= 32 only.
 #pragma once
 #include "mfma_blocks.h"
 #include "sac_rollout_device.h"
@@ -85,15 +93,17 @@ __device__ __forceinline__ bool kl_group_barrier(unsigned int* ctr, int C, unsig
 struct KSmem {
     lds_f32* hbuf;                       // [MBQ][LDH] (+16): activation image of the GEMM in flight
     lds_u8* mask;                        // [MB][MSTRIDE] bit 0: pi hidden (later V hidden), bit 1: Q(s,a) hidden
-    lds_f32* part_h;                     // [kWaves][MB][2]   mean | log_std head partials
+    lds_f32* part_h;                     // [kWaves][MB][2A]  mean | log_std head partials
     lds_f32* part_q;                     // [kWaves][MBQ]     one-column head partials (Q, V, Q at the nodes)
-    lds_f32* wvec;                       // [2][256] staged output-layer weights
+    lds_f32* wvec;                       // [2A][256] staged output-layer weights
     lds_f32 *x, *x2, *xq, *xn;           // [MB][SMAX]  s | s' | [s, a] | [s, a_new]
     lds_f32* z1s;                        // [MB][LDH]   Q's first-layer pre-activation without the action
-    lds_f32* w1a;                        // [256]       Q's first-layer action row
-    lds_f32 *node_a, *node_w, *node_u, *node_j;     // [KL_MAXNODES] node action, weight, atanh(a/amax), log(1 - (a/amax)^2 + 1e-6)
-    lds_f32 *a, *eps, *mu, *lsr, *sd, *z, *lp, *pls, *r, *g, *vt, *q, *qn, *v, *dq, *dvs;   // [MB]
-    lds_f32* dml;                        // [MB][2] seeds of the pi heads: d mean | d log_std (pre-clamp)
+    lds_f32* w1a;                        // [A][256]    Q's first-layer action rows
+    lds_f32 *node_a, *node_u;            // [KL_MAXNODES][A] node action, atanh(a/amax)
+    lds_f32 *node_w, *node_j;            // [KL_MAXNODES] weight, sum over the components of log(1 - (a/amax)^2 + 1e-6)
+    lds_f32 *a, *eps, *mu, *lsr, *sd, *z;                                    // [MB][A]; sd: std (A = 1), variance (A = 2)
+    lds_f32 *lp, *pls, *r, *g, *vt, *q, *qn, *v, *dq, *dvs;                  // [MB]
+    lds_f32* dml;                        // [MB][2A] seeds of the pi heads: d mean | d log_std (pre-clamp)
     lds_f32* red;                        // 16
     lds_f32* adam;                       // 4: alpha_pi, alpha_qv, eps
     lds_i64* idx;
@@ -117,7 +127,7 @@ __host__ __device__ inline size_t ksmem_carve(const RlcSacDims& d, int MT, int M
         off += (bytes + 15) & ~(size_t)15;
         return p;
     };
-    const int MB = MT * 16, MBQ = MTQ * 16, LDH = kl_mfma_ldh(d);
+    const int MB = MT * 16, MBQ = MTQ * 16, LDH = kl_mfma_ldh(d), A = d.A;
     const int MTX = MTQ > MT ? MTQ : MT;
     KSmem L;
     L.hbuf = (lds_f32*)take(sizeof(float) * (MTX * 16 * LDH + 16));
@@ -126,11 +136,11 @@ __host__ __device__ inline size_t ksmem_carve(const RlcSacDims& d, int MT, int M
     // the two partial buffers are never live together (a barrier separates every use of one from the next use of the
     // other): one region of the larger size
     {
-        const size_t bh = sizeof(float) * kWaves * MB * 2, bq = sizeof(float) * kWaves * MTX * 16;
+        const size_t bh = sizeof(float) * kWaves * MB * 2 * A, bq = sizeof(float) * kWaves * MTX * 16;
         L.part_h = (lds_f32*)take(bh > bq ? bh : bq);
         L.part_q = L.part_h;
     }
-    L.wvec = (lds_f32*)take(sizeof(float) * 2 * 256);
+    L.wvec = (lds_f32*)take(sizeof(float) * 2 * A * 256);
     // x (s) is a prefix of xq ([s, a]): the first-layer passes of pi and V read S columns of it and multiply the rest by
     // zero weights, so the two share one array
     lds_f32** ps[] = {&L.x2, &L.xq, &L.xn};
@@ -139,13 +149,16 @@ __host__ __device__ inline size_t ksmem_carve(const RlcSacDims& d, int MT, int M
     // at more than two batch tiles the first-layer image of Q (MB x LDH floats: 90 KB at seven tiles) lives in the agent's
     // global scratch instead (kl_z1s_in_global): the node passes read two or three of its rows each, L1-resident
     L.z1s = kl_z1s_in_global(MT) ? nullptr : (lds_f32*)take(sizeof(float) * MB * LDH);
-    L.w1a = (lds_f32*)take(sizeof(float) * 256);
-    lds_f32** pn[] = {&L.node_a, &L.node_w, &L.node_u, &L.node_j};
+    L.w1a = (lds_f32*)take(sizeof(float) * A * 256);
+    lds_f32** pna[] = {&L.node_a, &L.node_u};
+    for (auto p : pna) *p = (lds_f32*)take(sizeof(float) * KL_MAXNODES * A);
+    lds_f32** pn[] = {&L.node_w, &L.node_j};
     for (auto p : pn) *p = (lds_f32*)take(sizeof(float) * KL_MAXNODES);
-    lds_f32** pb[] = {&L.a, &L.eps, &L.mu, &L.lsr, &L.sd, &L.z, &L.lp, &L.pls, &L.r, &L.g, &L.vt, &L.q, &L.qn, &L.v,
-                      &L.dq, &L.dvs};
+    lds_f32** pa[] = {&L.a, &L.eps, &L.mu, &L.lsr, &L.sd, &L.z};
+    for (auto p : pa) *p = (lds_f32*)take(sizeof(float) * MB * A);
+    lds_f32** pb[] = {&L.lp, &L.pls, &L.r, &L.g, &L.vt, &L.q, &L.qn, &L.v, &L.dq, &L.dvs};
     for (auto p : pb) *p = (lds_f32*)take(sizeof(float) * MB);
-    L.dml = (lds_f32*)take(sizeof(float) * MB * 2);
+    L.dml = (lds_f32*)take(sizeof(float) * MB * 2 * A);
     L.red = (lds_f32*)take(sizeof(float) * 16);
     L.adam = (lds_f32*)take(sizeof(float) * 4);
     L.pool = (lds_i32*)take(sizeof(int) * 3 * RLC_MAX_BATCH);
@@ -172,7 +185,7 @@ __device__ __forceinline__ float kl_wave_sum(float v) {
     return v;
 }
 
-template <int MT, int MTQ, bool SPLIT = false>
+template <int MT, int MTQ, bool SPLIT = false, int AD = 1>
 __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev dv, int first_agent, int n_updates,
                                                                       int source, const long long* host_idx,
                                                                       const float* eps_in, int grad_taps,
@@ -180,7 +193,9 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using U = Blk<MT, KL_NTW, KL_MSTRIDE, true, true>;      // the three small networks: LERP target update, torch Adam
     using UQ = Blk<MTQ, KL_NTW, KL_MSTRIDE, true, true>;    // the node passes (forward only)
-    constexpr int MB = U::MB, MBQ = UQ::MB, NTW = KL_NTW, NS = 2;
+    constexpr int MB = U::MB, MBQ = UQ::MB, NTW = KL_NTW, NS = 2 * AD;
+    static_assert(AD == 1 || AD == 2, "the policy head, its log-density and the integrand's seeds are written for one or two action components");
+    static_assert(!(SPLIT && AD != 1), "latency mode is built for action_dim 1");
     const RlcSacDims d = dv.d;
     KSmem L;
     ksmem_carve(d, MT, MTQ, (lds_u8*)smem, &L);
@@ -221,8 +236,9 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
 
     // once per launch: zero the padded tails, stage the node tables
     for (int i = tid; i < MB * SMAX; i += kThreads) { L.x[i] = 0.f; L.x2[i] = 0.f; L.xq[i] = 0.f; L.xn[i] = 0.f; }
+    for (int i = tid; i < MB * AD; i += kThreads) { L.a[i] = 0.f; L.eps[i] = 0.f; L.mu[i] = 0.f; L.lsr[i] = 0.f; L.sd[i] = 0.f; L.z[i] = 0.f; }
     for (int i = tid; i < MB; i += kThreads) {
-        L.a[i] = 0.f; L.eps[i] = 0.f; L.mu[i] = 0.f; L.lsr[i] = 0.f; L.sd[i] = 0.f; L.z[i] = 0.f; L.lp[i] = 0.f; L.pls[i] = 0.f;
+        L.lp[i] = 0.f; L.pls[i] = 0.f;
         L.r[i] = 0.f; L.g[i] = 0.f; L.vt[i] = 0.f; L.q[i] = 0.f; L.qn[i] = 0.f; L.v[i] = 0.f; L.dq[i] = 0.f; L.dvs[i] = 0.f;
     }
     for (int i = tid; i < MB * NS; i += kThreads) L.dml[i] = 0.f;
@@ -230,22 +246,29 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
     for (int i = tid; i < MB * KL_MSTRIDE / 4; i += kThreads) reinterpret_cast<lds_u32*>(L.mask)[i] = 0u;
     for (int k = tid; k < KL_MAXNODES; k += kThreads) {
         const bool live = k < K;
-        const float an = live ? dv.kl_node_a[k] / amax0 : 0.0f;
-        L.node_a[k] = live ? dv.kl_node_a[k] : 0.0f;
         L.node_w[k] = live ? dv.kl_node_w[k] : 0.0f;
-        L.node_u[k] = (logf(1.0f + an) - logf(1.0f - an)) / 2.0f;       // PolicyNetwork.atanh (reversekl_network.py:384)
-        L.node_j[k] = logf(1.0f - an * an + EPS);
+        float corr = 0.0f;
+#pragma unroll
+        for (int j = 0; j < AD; j++) {
+            const float an = live ? dv.kl_node_a[k * AD + j] / amax0 : 0.0f;
+            L.node_a[k * AD + j] = live ? dv.kl_node_a[k * AD + j] : 0.0f;
+            L.node_u[k * AD + j] = (logf(1.0f + an) - logf(1.0f - an)) / 2.0f;       // PolicyNetwork.atanh (reversekl_network.py:384)
+            corr += logf(1.0f - an * an + EPS);
+        }
+        L.node_j[k] = corr;
     }
     if (tid < 16) L.hbuf[(MBQ > MB ? MBQ : MB) * LDH + tid] = 0.0f;
     __syncthreads();
 
     // Q at the rows [p0, p0 + 16 MTQ) of the B x K (state, node) grid for every pass p0 this workgroup takes (SPLIT: pass
-    // index mod C == c_split): layer 1 = relu(z1s[b] + a_k W1[action row]) written straight into the activation image
+    // index mod C == c_split): layer 1 = relu(z1s[b] + sum_j a_kj W1[action row j]) written straight into the activation image
     const int NQ = LDH >> 2;                           // column quads of a row of the activation image
     auto node_passes = [&]() {
         const int cq = tid % NQ, r0t = tid / NQ, rstep = kThreads / NQ;
         const bool filler = tid < rstep * NQ;
-        const f32x4 wa = *reinterpret_cast<const lds_f32x4*>(&L.w1a[cq << 2]);
+        f32x4 wa[AD];
+#pragma unroll
+        for (int j = 0; j < AD; j++) wa[j] = *reinterpret_cast<const lds_f32x4*>(&L.w1a[j * 256 + (cq << 2)]);
         const float qb3 = th[d.qb3];
         for (int p0 = 0; p0 < rows; p0 += MBQ) {
             if (SPLIT && (p0 / MBQ) % sp.C != c_split) continue;
@@ -258,9 +281,16 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                         f32x4 zz;
                         if constexpr (ZG) zz = *reinterpret_cast<const f32x4*>(&z1g[b * LDH + (cq << 2)]);
                         else zz = *reinterpret_cast<const lds_f32x4*>(&L.z1s[b * LDH + (cq << 2)]);
-                        const float ak = L.node_a[k];
+                        if constexpr (AD == 1) {
+                            const float ak = L.node_a[k];
 #pragma unroll
-                        for (int e = 0; e < 4; e++) o[e] = fmaxf(zz[e] + ak * wa[e], 0.0f);
+                            for (int e = 0; e < 4; e++) o[e] = fmaxf(zz[e] + ak * wa[0][e], 0.0f);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < AD; j++) zz += L.node_a[k * AD + j] * wa[j];
+#pragma unroll
+                            for (int e = 0; e < 4; e++) o[e] = fmaxf(zz[e], 0.0f);
+                        }
                     }
                     *reinterpret_cast<lds_f32x4*>(&L.hbuf[i * LDH + (cq << 2)]) = o;
                 }
@@ -286,7 +316,7 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                 if constexpr (!ZG)
                     for (int i = tid; i < (MB * LDH) >> 2; i += kThreads)
                         reinterpret_cast<lds_f32x4*>(L.z1s)[i] = reinterpret_cast<const f32x4*>(zb)[i];
-                for (int n = tid; n < 256; n += kThreads) L.w1a[n] = n < L1C ? th[d.qW1 + S * L1C + n] : 0.0f;
+                for (int n = tid; n < AD * 256; n += kThreads) L.w1a[n] = (n & 255) < L1C ? th[d.qW1 + (S + (n >> 8)) * L1C + (n & 255)] : 0.0f;
                 __syncthreads();
                 node_passes();
                 if (!kl_group_barrier(sp.bar + rel_agent, sp.C, bar_gen, sp.err, L.dups + 3)) return;
@@ -319,11 +349,11 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
             const float *ps, *pa, *ps2;
             if (source == RLC_SRC_STAGING) {
                 const size_t slot = (size_t)agent * RLC_MAX_BATCH + b;
-                ps = dv.rep.gs + slot * S; pa = dv.rep.ga + slot; ps2 = dv.rep.gs2 + slot * S;
+                ps = dv.rep.gs + slot * S; pa = dv.rep.ga + slot * AD; ps2 = dv.rep.gs2 + slot * S;
                 L.r[b] = (float)dv.rep.gr[slot]; L.g[b] = (float)dv.rep.gg[slot];
             } else {
                 const size_t slot = (size_t)agent * dv.rep.cap + ring_slot(ring, dv.rep.cap, L.idx[b]);
-                ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot; ps2 = dv.rep.rs2 + slot * S;
+                ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot * AD; ps2 = dv.rep.rs2 + slot * S;
                 L.r[b] = (float)dv.rep.rr[slot]; L.g[b] = (float)dv.rep.rg[slot];
             }
             for (int i = 0; i < S; i++) {
@@ -331,18 +361,22 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                 L.x[b * SMAX + i] = sv; L.xq[b * SMAX + i] = sv; L.xn[b * SMAX + i] = sv;
                 L.x2[b * SMAX + i] = ps2[i];
             }
-            L.a[b] = pa[0];
-            L.xq[b * SMAX + S] = pa[0];
-            float e;
-            if (eps_in) {
-                e = eps_in[((size_t)rel_agent * n_updates + upd) * B + b];
-            } else {
-                const Philox4 p = philox4x32_10(dv.rep.seed[agent] ^ RLC_KEY_SAC_EPS, nctr, (unsigned long long)b >> 1);
-                float n0, n1;
-                philox_normal2(p, n0, n1);
-                e = (b & 1) ? n1 : n0;
+#pragma unroll
+            for (int j = 0; j < AD; j++) {
+                const int at = b * AD + j;
+                L.a[at] = pa[j];
+                L.xq[b * SMAX + S + j] = pa[j];
+                float e;
+                if (eps_in) {
+                    e = eps_in[((size_t)rel_agent * n_updates + upd) * B * AD + at];
+                } else {
+                    const Philox4 p = philox4x32_10(dv.rep.seed[agent] ^ RLC_KEY_SAC_EPS, nctr, (unsigned long long)at >> 1);
+                    float n0, n1;
+                    philox_normal2(p, n0, n1);
+                    e = (at & 1) ? n1 : n0;
+                }
+                L.eps[at] = e;
             }
-            L.eps[b] = e;
         }
         if (tid == 0) {
             // torch's Adam as the TF-form step with alpha = lr * c / (1 - b1^t), epsilon = 1e-8 * c, c = sqrt(1 - b2^t)
@@ -368,9 +402,9 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
         // ================= 2: pi forward, the draw and its log-density (reversekl_network.py:332-357) =================
         u.H1 = L1A;
         u.trunk(th + d.pW1, th + d.pb1, L.x);
-        for (int i = tid; i < NS * 256; i += kThreads) {      // row 0: mean head, row 1: log_std head
+        for (int i = tid; i < NS * 256; i += kThreads) {      // rows 0..A-1: mean heads, rows A..2A-1: log_std heads
             const int j = i / 256, n = i % 256;
-            L.wvec[i] = n < L2A ? (j == 0 ? th[d.pWm + n] : th[d.pWs + n]) : 0.0f;
+            L.wvec[i] = n < L2A ? (j < AD ? th[d.pWm + n * AD + j] : th[d.pWs + n * AD + (j - AD)]) : 0.0f;
         }
         __syncthreads();
         u.fwd_gemm(acc, th + d.pW2, L2A, L1A);
@@ -384,20 +418,43 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
             for (int i = 0; i < NTW; i++) acch[mt][i] = acc[mt][i];
         __syncthreads();
         for (int b = tid; b < B; b += kThreads) {
-            const float mu = u.template part_sum<NS>(L.part_h, b, 0) + th[d.pbm];
-            const float lsr = u.template part_sum<NS>(L.part_h, b, 1) + th[d.pbs];
-            const float ls = fminf(fmaxf(lsr, -20.0f), 2.0f);
-            const float sd = expf(ls);
-            const float z = mu + sd * L.eps[b];
-            const float t = tanhf(z);
-            const float dz = z - mu;
-            const float lp = -(dz * dz) / (2.0f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI - logf(1.0f - t * t + EPS);
-            L.mu[b] = mu; L.lsr[b] = lsr; L.sd[b] = sd; L.z[b] = z; L.lp[b] = lp;
-            L.xn[b * SMAX + S] = t * amax0;
+            float lp;
+            if constexpr (AD == 1) {
+                const float mu = u.template part_sum<NS>(L.part_h, b, 0) + th[d.pbm];
+                const float lsr = u.template part_sum<NS>(L.part_h, b, 1) + th[d.pbs];
+                const float ls = fminf(fmaxf(lsr, -20.0f), 2.0f);
+                const float sd = expf(ls);
+                const float z = mu + sd * L.eps[b];
+                const float t = tanhf(z);
+                const float dz = z - mu;
+                lp = -(dz * dz) / (2.0f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI - logf(1.0f - t * t + EPS);
+                L.mu[b] = mu; L.lsr[b] = lsr; L.sd[b] = sd; L.z[b] = z;
+                L.xn[b * SMAX + S] = t * amax0;
+            } else {
+                // covariance diag(std): component j has variance std_j (L.sd holds it), standard deviation sqrt(std_j)
+                float quad = 0.0f, corr = 0.0f;
+#pragma unroll
+                for (int j = 0; j < AD; j++) {
+                    const int at = b * AD + j;
+                    const float mu = u.template part_sum<NS>(L.part_h, b, j) + th[d.pbm + j];
+                    const float lsr = u.template part_sum<NS>(L.part_h, b, AD + j) + th[d.pbs + j];
+                    const float ls = fminf(fmaxf(lsr, -20.0f), 2.0f);
+                    const float var = expf(ls), sq = sqrtf(var);
+                    const float z = mu + sq * L.eps[at];
+                    const float t = tanhf(z);
+                    const float dz = z - mu;
+                    quad += -(dz * dz) / (2.0f * var) - logf(sq);
+                    corr += logf(1.0f - t * t + EPS);
+                    L.mu[at] = mu; L.lsr[at] = lsr; L.sd[at] = var; L.z[at] = z;
+                    L.xn[b * SMAX + S + j] = t * amax0;
+                }
+                lp = quad - (float)AD * LOG_SQRT_2PI - corr;
+            }
+            L.lp[b] = lp;
             dv.tap_logp[(size_t)agent * RLC_MAX_BATCH + b] = lp;
         }
         // ================= 3: Q(s,a), its seeds and wave-local column reductions =================
-        u.S = S + 1; u.H1 = L1C;
+        u.S = S + AD; u.H1 = L1C;
         u.trunk(th + d.qW1, th + d.qb1, L.xq);
         __syncthreads();
         f32x4 accq[MT][NTW];
@@ -466,7 +523,7 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
         float pl = 0.0f;
         if (integral) {
             // ================= 6: Q at the quadrature nodes =================
-            // z1s[b] = s_b W1[:S] + b1 (no relu), the action row of W1
+            // z1s[b] = s_b W1[:S] + b1 (no relu), the action rows of W1
             for (int e = tid; e < B * NQ; e += kThreads) {
                 const int b = e / NQ, n0 = (e % NQ) << 2;
                 f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -479,7 +536,7 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                 else *reinterpret_cast<lds_f32x4*>(&L.z1s[b * LDH + n0]) = o;
                 if constexpr (SPLIT) *reinterpret_cast<f32x4*>(&sp.zbuf[(size_t)rel_agent * MB * LDH + b * LDH + n0]) = o;
             }
-            for (int n = tid; n < 256; n += kThreads) L.w1a[n] = n < L1C ? th[d.qW1 + S * L1C + n] : 0.0f;
+            for (int n = tid; n < AD * 256; n += kThreads) L.w1a[n] = (n & 255) < L1C ? th[d.qW1 + (S + (n >> 8)) * L1C + (n & 255)] : 0.0f;
             __syncthreads();
             if constexpr (SPLIT) { if (!kl_group_barrier(sp.bar + rel_agent, sp.C, bar_gen, sp.err, L.dups + 3)) return; }     // z1s published
             node_passes();
@@ -487,7 +544,7 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
             __syncthreads();
             // ================= 7: one wave per state: log pi at the nodes, d loss / d lp, seeds of mean and log_std =================
             for (int b = u.wave; b < B; b += kWaves) {
-                const float mu = L.mu[b], sd = L.sd[b], var = sd * sd, lsd = logf(sd), vb = L.v[b];
+                const float vb = L.v[b];
                 float shift = -INFINITY, zsum = 0.0f;
                 if (dv.kl_kind == RLC_KL_FORWARD) {
                     for (int k = u.lane; k < K; k += 64) shift = fmaxf(shift, iq[b * K + k] / alpha_ent);
@@ -496,10 +553,9 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                     for (int k = u.lane; k < K; k += 64) zsum += expf(iq[b * K + k] / alpha_ent - shift) * L.node_w[k];
                     zsum = kl_wave_sum(zsum);
                 }
-                float gm = 0.0f, gs = 0.0f, loss = 0.0f;
-                for (int k = u.lane; k < K; k += 64) {
-                    const float w = L.node_w[k], du = L.node_u[k] - mu;
-                    const float lp = -(du * du) / (2.0f * var) - lsd - LOG_SQRT_2PI - L.node_j[k];
+                // the integrand's coefficient d loss_b / d lp_k is a scalar per node whatever the action dimension
+                auto node_coef = [&](int k, float lp, float& loss) {
+                    const float w = L.node_w[k];
                     float coef;
                     if (dv.kl_kind == RLC_KL_FORWARD) {
                         const float bp = expf(iq[b * K + k] / alpha_ent - shift) / zsum;
@@ -515,14 +571,51 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
                             coef = -e * adv * w;
                         }
                     }
-                    gm += coef * (du / var);
-                    gs += coef * (du * du / var - 1.0f);
+                    return coef;
+                };
+                float gm[AD], gs[AD], loss = 0.0f;
+#pragma unroll
+                for (int j = 0; j < AD; j++) { gm[j] = 0.0f; gs[j] = 0.0f; }
+                if constexpr (AD == 1) {
+                    const float mu = L.mu[b], sd = L.sd[b], var = sd * sd, lsd = logf(sd);
+                    for (int k = u.lane; k < K; k += 64) {
+                        const float du = L.node_u[k] - mu;
+                        const float lp = -(du * du) / (2.0f * var) - lsd - LOG_SQRT_2PI - L.node_j[k];
+                        const float coef = node_coef(k, lp, loss);
+                        gm[0] += coef * (du / var);
+                        gs[0] += coef * (du * du / var - 1.0f);
+                    }
+                } else {
+                    float mu[AD], var[AD], lsq[AD];
+#pragma unroll
+                    for (int j = 0; j < AD; j++) { mu[j] = L.mu[b * AD + j]; var[j] = L.sd[b * AD + j]; lsq[j] = logf(sqrtf(var[j])); }
+                    for (int k = u.lane; k < K; k += 64) {
+                        float du[AD], quad = 0.0f;
+#pragma unroll
+                        for (int j = 0; j < AD; j++) {
+                            du[j] = L.node_u[k * AD + j] - mu[j];
+                            quad += -(du[j] * du[j]) / (2.0f * var[j]) - lsq[j];
+                        }
+                        const float lp = quad - (float)AD * LOG_SQRT_2PI - L.node_j[k];
+                        const float coef = node_coef(k, lp, loss);
+#pragma unroll
+                        for (int j = 0; j < AD; j++) {
+                            gm[j] += coef * (du[j] / var[j]);
+                            gs[j] += coef * (du[j] * du[j] / (2.0f * var[j]) - 0.5f);
+                        }
+                    }
                 }
-                gm = kl_wave_sum(gm); gs = kl_wave_sum(gs); loss = kl_wave_sum(loss);
+#pragma unroll
+                for (int j = 0; j < AD; j++) { gm[j] = kl_wave_sum(gm[j]); gs[j] = kl_wave_sum(gs[j]); }
+                loss = kl_wave_sum(loss);
                 if (u.lane == 0) {
-                    const bool inside = L.lsr[b] >= -20.0f && L.lsr[b] <= 2.0f;
-                    L.dml[b * NS + 0] = gm * invB;
-                    L.dml[b * NS + 1] = inside ? gs * invB : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < AD; j++) {
+                        const float lsr = L.lsr[b * AD + j];
+                        const bool inside = lsr >= -20.0f && lsr <= 2.0f;
+                        L.dml[b * NS + j] = gm[j] * invB;
+                        L.dml[b * NS + AD + j] = inside ? gs[j] * invB : 0.0f;
+                    }
                     L.pls[b] = loss;
                 }
             }
@@ -530,11 +623,17 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
             // ll / hard_ll: -log_prob * (advantage).detach() on the drawn z
             for (int b = tid; b < B; b += kThreads) {
                 const float adv = (L.qn[b] - L.v[b]) - (dv.kl_optim == RLC_KL_OPTIM_LL ? alpha_ent * L.lp[b] : 0.0f);
-                const float coef = -adv * invB, dz = L.z[b] - L.mu[b], var = L.sd[b] * L.sd[b];
-                const bool inside = L.lsr[b] >= -20.0f && L.lsr[b] <= 2.0f;
+                const float coef = -adv * invB;
                 L.pls[b] = -L.lp[b] * adv;
-                L.dml[b * NS + 0] = coef * dz / var;
-                L.dml[b * NS + 1] = inside ? coef * (dz * dz / var - 1.0f) : 0.0f;
+#pragma unroll
+                for (int j = 0; j < AD; j++) {
+                    const int at = b * AD + j;
+                    const float dz = L.z[at] - L.mu[at], var = AD == 1 ? L.sd[at] * L.sd[at] : L.sd[at];
+                    const bool inside = L.lsr[at] >= -20.0f && L.lsr[at] <= 2.0f;
+                    L.dml[b * NS + j] = coef * dz / var;
+                    // d log N / d log_std: variance std^2 (one dimension) or std (the diag(std) covariance)
+                    L.dml[b * NS + AD + j] = !inside ? 0.0f : AD == 1 ? coef * (dz * dz / var - 1.0f) : coef * (dz * dz / (2.0f * var) - 0.5f);
+                }
             }
         }
         __syncthreads();
@@ -587,24 +686,29 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
             for (int i = 0; i < NTW; i++) {
                 const int t = u.tile_of(i);
                 const int n = 16 * t + u.c;
-                if (t < NT && n < L2A && u.g <= NS) {
-                    // lane group 0 -> pb2[n]; 1 -> Wm[n]; 2 -> Ws[n]
-                    const int p = u.g == 0 ? d.pb2 + n : (u.g == 1 ? d.pWm + n : d.pWs + n);
-                    const float gr = u.g == 0 ? g_pb2[i] : (u.g == 1 ? g_ph[i][0] : g_ph[i][1]);
-                    u.adam_scalar_m(th, mm, vv, nullptr, tapg, p, gr, alpha_p, 0.0f);
+                if (t < NT && n < L2A) {
+                    // lane group 0 -> pb2[n]; targets 1..A -> Wm[n][j]; A+1..2A -> Ws[n][j]
+                    for (int tg = u.g; tg <= NS; tg += 4) {
+                        int p = d.pb2 + n;
+                        float gr = g_pb2[i];
+#pragma unroll
+                        for (int j = 0; j < NS; j++)
+                            if (tg == j + 1) { p = (j < AD ? d.pWm + n * AD + j : d.pWs + n * AD + (j - AD)); gr = g_ph[i][j]; }
+                        u.adam_scalar_m(th, mm, vv, nullptr, tapg, p, gr, alpha_p, 0.0f);
+                    }
                 }
             }
-            if (u.wave < NS) {            // bm / bs: sum_b of the seeds, wave j
+            if (u.wave < NS) {            // bm[j] / bs[j]: sum_b of the seeds, wave j
                 const int j = u.wave;
                 float gr = 0.0f;
                 for (int b = u.lane; b < MB; b += 64) gr += L.dml[b * NS + j];
                 gr = kl_wave_sum(gr);
-                if (u.lane == 0) u.adam_scalar_m(th, mm, vv, nullptr, tapg, j == 0 ? d.pbm : d.pbs, gr, alpha_p, 0.0f);
+                if (u.lane == 0) u.adam_scalar_m(th, mm, vv, nullptr, tapg, j < AD ? d.pbm + j : d.pbs + (j - AD), gr, alpha_p, 0.0f);
             }
         }
         __syncthreads();
         // ================= 9: Q step =================
-        u.S = S + 1; u.H1 = L1C;
+        u.S = S + AD; u.H1 = L1C;
         u.trunk(th + d.qW1, th + d.qb1, L.xq);
         for (int n = tid; n < 256; n += kThreads) L.wvec[n] = n < L2C ? th[d.qW3 + n] : 0.0f;
         __syncthreads();
@@ -726,12 +830,12 @@ int kl_launch_split_t(const RlcSacDev& dv, const KlSplit& sp, int first_agent, i
     return 0;
 }
 
-template <int MT, int MTQ>
+template <int MT, int MTQ, int AD = 1>
 int kl_launch_t(const RlcSacDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
                 const float* eps_dev, int grad_taps, hipStream_t st, const RlcSacRollout* rollout) {
     const size_t lds = ksmem_carve(dv.d, MT, MTQ, nullptr, nullptr);
     RLC_REQUIRE(lds <= 160 * 1024, "MFMA KL kernel needs %zu B of LDS (> 160 KiB)", lds);
-    auto kern = rlc_kl_update_mfma_kernel<MT, MTQ, false>;
+    auto kern = rlc_kl_update_mfma_kernel<MT, MTQ, false, AD>;
     static bool attr_set = false;
     if (!attr_set) {
         RLC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -48,10 +48,11 @@ int rlc_kl_create(const rlc_kl_config* cfg, rlc_handle** out) {
     RlcSacDev& dv = h->sac;
     dv.d = rlc_sac_make_dims(cfg->state_dim, cfg->action_dim, cfg->actor_l1_dim, cfg->actor_l2_dim, cfg->critic_l1_dim,
                              cfg->critic_l2_dim, cfg->batch_size, 0, 1);
-    // the tile-blocked weight layout goes with the MFMA kernel (the default whenever it supports the shape)
+    // the tile-blocked weight layout goes with the MFMA kernel: the default whenever it supports the shape at
+    // action_dim 1; above that it is chosen by rlc_kl_set_kernel only, and a new population runs the any-shape kernel
     {
         const bool integral_ = cfg->optim_type == RLC_KL_OPTIM_INTG || cfg->optim_type == RLC_KL_OPTIM_HARD_INTG;
-        if (rlc_kl_mfma_supported(dv.d, integral_ ? cfg->n_nodes : 0))
+        if (cfg->action_dim == 1 && rlc_kl_mfma_supported(dv.d, integral_ ? cfg->n_nodes : 0))
             dv.d = rlc_sac_make_dims(cfg->state_dim, cfg->action_dim, cfg->actor_l1_dim, cfg->actor_l2_dim,
                                      cfg->critic_l1_dim, cfg->critic_l2_dim, cfg->batch_size, 1, 1);
     }
@@ -128,8 +129,10 @@ int rlc_kl_set_kernel(rlc_handle* h, int32_t variant) {
     RLC_REQUIRE(h, "null handle");
     RLC_NEED_KL(h);
     RLC_REQUIRE(variant >= 0 && variant <= 2, "kernel variant must be 0 (auto), 1 (generic) or 2 (mfma)");
-    RLC_REQUIRE(variant != 2 || rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes),
-                "MFMA KL kernel does not support these dimensions");
+    if (variant == 2) {
+        const char* why = rlc_kl_mfma_refusal(h->sac.d, h->sac.kl_nodes);
+        RLC_REQUIRE(!why, "MFMA KL kernel does not support these dimensions: %s", why);
+    }
     h->variant = variant;
     if (rlc_h_kl_variant(h) != 2) h->split_c = 1;        // latency mode belongs to the MFMA kernel
     return rlc_h_sac_relayout(h, rlc_h_kl_variant(h) == 2 ? 1 : 0);
@@ -143,6 +146,7 @@ int rlc_kl_set_split(rlc_handle* h, int32_t n_workgroups) {
     RLC_REQUIRE(!h->has_env, "the on-device experiment loop runs the one-workgroup kernels");
     if (n_workgroups == 1) { h->split_c = 1; return 0; }
     RLC_REQUIRE(rlc_h_kl_variant(h) == 2, "latency mode is a variant of the MFMA kernel (these dimensions run the any-shape one)");
+    RLC_REQUIRE(h->sac.d.A == 1, "latency mode of the KL agents is built for action_dim 1 (got %d)", h->sac.d.A);
     RLC_REQUIRE(h->sac.kl_optim == RLC_KL_OPTIM_INTG || h->sac.kl_optim == RLC_KL_OPTIM_HARD_INTG,
                 "latency mode splits the action integral; the 'll' updates have none");
     hipDeviceProp_t prop;

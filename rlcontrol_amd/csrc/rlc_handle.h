@@ -68,7 +68,8 @@ inline int rlc_h_sac_variant(const rlc_handle* h) {
 }
 inline int rlc_h_kl_variant(const rlc_handle* h) {
     if (h->variant == 1 || h->variant == 2) return h->variant;
-    return rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes) ? 2 : 1;
+    // above one action dimension the MFMA kernel is opt-in (rlc_kl_set_kernel)
+    return (h->sac.d.A == 1 && rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes)) ? 2 : 1;
 }
 inline int rlc_h_naf_variant(const rlc_handle* h) {
     if (h->variant == 1 || h->variant == 2) return h->variant;
