@@ -5,14 +5,12 @@
 #include "sac_rollout_device.h"
 #include "naf_rollout_device.h"
 
-#define RLC_NEED_DDPG(h) RLC_REQUIRE((h) && (h)->algo == RLC_ALGO_DDPG, "handle is not a DDPG population")
 #define RLC_NEED_ENV(h) RLC_REQUIRE((h) && (h)->has_env, "no rollout configured on this handle (rlc_ddpg_rollout_create)")
 
 // n training steps of every agent in ONE launch of the fused update kernel
 static int launch_steps(rlc_handle* h, int n, int q8_first) {
     const RlcDev& dv = h->dv;
-    const bool mfma = h->variant == 2 || (h->variant == 0 && rlc_mfma_supported(dv.d));
-    if (mfma)
+    if (rlc_h_variant(h) == 2)
         return rlc_launch_ddpg_update_mfma(dv, 0, dv.n_agents, n, RLC_SRC_REPLAY_DEVICE_SAMPLER, nullptr, 0, h->st,
                                            h->rollout_dev, q8_first);
     return rlc_launch_ddpg_update_generic(dv, 0, dv.n_agents, n, RLC_SRC_REPLAY_DEVICE_SAMPLER, nullptr, 0, h->st,
@@ -65,7 +63,7 @@ static int rollout_alloc(rlc_handle* h, const rlc_rollout_config* cfg) {
 
 int rlc_ddpg_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg) {
     RLC_REQUIRE(h && cfg, "null argument");
-    RLC_NEED_DDPG(h);
+    RLC_NEED(h, RLC_ALGO_DDPG);
     if (rollout_alloc(h, cfg)) return 1;
     // device-resident argument block of the fused launches
     if (rlc_h_malloc(h, &h->rollout_dev, 1)) return 1;
@@ -93,19 +91,19 @@ static int sacfam_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg) {
 
 int rlc_sac_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg) {
     RLC_REQUIRE(h && cfg, "null argument");
-    RLC_REQUIRE(h->algo == RLC_ALGO_SAC, "handle is not a SoftActorCritic population");
+    RLC_NEED(h, RLC_ALGO_SAC);
     return sacfam_rollout_create(h, cfg);
 }
 
 int rlc_kl_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg) {
     RLC_REQUIRE(h && cfg, "null argument");
-    RLC_REQUIRE(h->algo == RLC_ALGO_KL, "handle is not a ReverseKL / ForwardKL population");
+    RLC_NEED(h, RLC_ALGO_KL);
     return sacfam_rollout_create(h, cfg);
 }
 
 int rlc_naf_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg, const float* noise_scale) {
     RLC_REQUIRE(h && cfg && noise_scale, "null argument");
-    RLC_REQUIRE(h->algo == RLC_ALGO_NAF, "handle is not a NAF population");
+    RLC_NEED(h, RLC_ALGO_NAF);
     if (rollout_alloc(h, cfg)) return 1;
     const size_t NA = h->naf.n_agents;
     float* ns_dev;
@@ -179,25 +177,25 @@ static int rollout_run(rlc_handle* h, int64_t n_steps, int64_t* out_total_steps)
 
 int rlc_ddpg_rollout_run(rlc_handle* h, int64_t n_steps, int64_t* out_total_steps) {
     RLC_NEED_ENV(h);
-    RLC_NEED_DDPG(h);
+    RLC_NEED(h, RLC_ALGO_DDPG);
     return rollout_run(h, n_steps, out_total_steps);
 }
 
 int rlc_sac_rollout_run(rlc_handle* h, int64_t n_steps, int64_t* out_total_steps) {
     RLC_NEED_ENV(h);
-    RLC_REQUIRE(h->algo == RLC_ALGO_SAC, "handle is not a SoftActorCritic population");
+    RLC_NEED(h, RLC_ALGO_SAC);
     return rollout_run(h, n_steps, out_total_steps);
 }
 
 int rlc_kl_rollout_run(rlc_handle* h, int64_t n_steps, int64_t* out_total_steps) {
     RLC_NEED_ENV(h);
-    RLC_REQUIRE(h->algo == RLC_ALGO_KL, "handle is not a ReverseKL / ForwardKL population");
+    RLC_NEED(h, RLC_ALGO_KL);
     return rollout_run(h, n_steps, out_total_steps);
 }
 
 int rlc_naf_rollout_run(rlc_handle* h, int64_t n_steps, int64_t* out_total_steps) {
     RLC_NEED_ENV(h);
-    RLC_REQUIRE(h->algo == RLC_ALGO_NAF, "handle is not a NAF population");
+    RLC_NEED(h, RLC_ALGO_NAF);
     return rollout_run(h, n_steps, out_total_steps);
 }
 

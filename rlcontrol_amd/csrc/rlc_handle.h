@@ -2,6 +2,10 @@
 // a population of independent agents of ONE algorithm on one GPU.  The replay ring, the staging buffers,
 // the stream and the timer are common; the networks and optimizer state are per algorithm.
 #pragma once
+#include <string.h>
+
+#include <string>
+
 #include "rlc_common.h"
 #include "sac_common.h"
 #include "naf_common.h"
@@ -51,29 +55,88 @@ struct rlc_handle {
     int ro_pending_q8;                   // an evaluation ran after the last update: next step resets OU after acting
 };
 
-// kernel variant in use (1 generic, 2 mfma): the request h->variant (0 auto) resolved against the shape support
 // Latency-mode launches (ddpg_split.hip / kl_mfma.hip): the error word is cleared before every launch (set instead when
 // the test hook asked for a failure) and read back after it.  On failure every workgroup has left the kernel at the
 // barrier that failed, before any store of the phase behind it: parameters / optimizer state are those of the last
 // COMPLETED phase of the failed update.  The handle then refuses latency-mode updates until rlc_*_set_split re-arms it
 // (after the caller has reloaded or accepted the state).
-extern "C" {
 int rlc_h_split_before_launch(rlc_handle* h);
 int rlc_h_split_after_launch(rlc_handle* h);
+
+// ---- what differs between the algorithms on the host side is data: the tables below; the bodies are in rlc_api.hip ----
+inline const char* rlc_algo_name(int algo) {
+    return algo == RLC_ALGO_DDPG ? "DDPG" : algo == RLC_ALGO_SAC ? "SoftActorCritic" : algo == RLC_ALGO_NAF ? "NAF"
+                                                                                      : "ReverseKL / ForwardKL";
+}
+#define RLC_NEED(h, a) RLC_REQUIRE((h) && (h)->algo == (a), "handle is not a %s population", rlc_algo_name(a))
+
+// f(device view of the handle's algorithm)
+template <class F>
+int rlc_h_with_dev(rlc_handle* h, F f) {
+    return h->algo == RLC_ALGO_DDPG ? f(h->dv) : h->algo == RLC_ALGO_NAF ? f(h->naf) : f(h->sac);
 }
 
-inline int rlc_h_sac_variant(const rlc_handle* h) {
-    if (h->variant == 1 || h->variant == 2) return h->variant;
-    return rlc_sac_mfma_supported(h->sac.d) ? 2 : 1;
+// the per-agent parameter-shaped blobs [n_agents][Ppad], in the order of the ABI's blob selector
+inline std::vector<float**> rlc_blobs(RlcDev& v) { return {&v.theta, &v.theta_t, &v.m_a, &v.v_a, &v.m_c, &v.v_c}; }
+inline std::vector<float**> rlc_blobs(RlcSacDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
+inline std::vector<float**> rlc_blobs(RlcNafDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
+// the gradient taps, blobs that exist only after *_enable_grad_taps
+inline std::vector<float**> rlc_grad_taps(RlcDev& v) { return {&v.tap_gc, &v.tap_ga}; }
+inline std::vector<float**> rlc_grad_taps(RlcSacDev& v) { return {&v.tap_g}; }
+inline std::vector<float**> rlc_grad_taps(RlcNafDev& v) { return {&v.tap_g}; }
+// the same dims with the other weight layout
+inline RlcDims rlc_with_layout(const RlcDims& d, int blocked) {
+    return rlc_make_dims(d.S, d.A, d.H1, d.HA, d.HC, d.B, blocked, d.norm, d.sep);
 }
-inline int rlc_h_kl_variant(const rlc_handle* h) {
-    if (h->variant == 1 || h->variant == 2) return h->variant;
-    // above one action dimension the MFMA kernel is opt-in (rlc_kl_set_kernel)
-    return (h->sac.d.A == 1 && rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes)) ? 2 : 1;
+inline RlcSacDims rlc_with_layout(const RlcSacDims& d, int blocked) {
+    return rlc_sac_make_dims(d.S, d.A, d.L1A, d.L2A, d.L1C, d.L2C, d.B, blocked, d.qcat, d.norm);
 }
-inline int rlc_h_naf_variant(const rlc_handle* h) {
+inline RlcNafDims rlc_with_layout(const RlcNafDims& d, int blocked) {
+    return rlc_naf_make_dims(d.S, d.A, d.L1, d.L2, d.B, blocked, d.norm);
+}
+inline int rlc_beta_powers(const RlcDev&) { return 4; }
+inline int rlc_beta_powers(const RlcSacDev&) { return 4; }
+inline int rlc_beta_powers(const RlcNafDev&) { return 2; }
+// tap `which` of the last update: all agents' array (null: not available), per-agent stride, floats the caller gets,
+// blob = stored in the padded device layout of a parameter blob
+struct RlcTap { const float* base; size_t stride; long long len; bool blob; };
+inline RlcTap rlc_tap(const RlcDev& v, int which, int B) {
+    const size_t MB = RLC_MAX_BATCH, A = v.d.A;
+    const RlcTap t[] = {{v.tap_q, MB, B, false},
+                        {v.tap_y, MB, B, false},
+                        {v.tap_aout, MB * A, B * (long long)A, false},
+                        {v.tap_dqda, MB * A, B * (long long)A, false},
+                        {v.tap_gc, (size_t)v.d.Ppad, v.d.P, true},
+                        {v.tap_ga, (size_t)v.d.Ppad, v.d.P, true}};
+    return which >= 0 && which < 6 ? t[which] : RlcTap{nullptr, 0, 0, false};
+}
+inline RlcTap rlc_tap(const RlcSacDev& v, int which, int B) {
+    const size_t MB = RLC_MAX_BATCH, IQ = (size_t)B * v.kl_nodes;
+    const RlcTap t[] = {{v.tap_q, MB, B, false},
+                        {v.tap_v, MB, B, false},
+                        {v.tap_logp, MB, B, false},
+                        {v.tap_qpi, MB, B, false},
+                        {v.tap_loss, 4, 3, false},
+                        {v.tap_g, (size_t)v.d.Ppad, v.d.P, true},
+                        {v.kl_tap_iq, IQ, (long long)IQ, false}};      // Q at the quadrature nodes: KL populations only
+    return which >= 0 && which < 7 ? t[which] : RlcTap{nullptr, 0, 0, false};
+}
+inline RlcTap rlc_tap(const RlcNafDev& v, int which, int B) {
+    const size_t MB = RLC_MAX_BATCH;
+    const RlcTap t[] = {{v.tap_q, MB, B, false}, {v.tap_y, MB, B, false}, {v.tap_V, MB, B, false},
+                        {v.tap_g, (size_t)v.d.Ppad, v.d.P, true}};
+    return which >= 0 && which < 4 ? t[which] : RlcTap{nullptr, 0, 0, false};
+}
+// kernel variant in use (1 generic, 2 mfma): the request h->variant (0 auto) resolved against the shape support
+inline int rlc_h_variant(const rlc_handle* h) {
     if (h->variant == 1 || h->variant == 2) return h->variant;
-    return rlc_naf_mfma_supported(h->naf.d) ? 2 : 1;
+    switch (h->algo) {
+        case RLC_ALGO_DDPG: return rlc_mfma_supported(h->dv.d) ? 2 : 1;
+        case RLC_ALGO_SAC: return rlc_sac_mfma_supported(h->sac.d) ? 2 : 1;
+        case RLC_ALGO_NAF: return rlc_naf_mfma_supported(h->naf.d) ? 2 : 1;
+        // above one action dimension the KL MFMA kernel is opt-in (rlc_kl_set_kernel)
+        default: return (h->sac.d.A == 1 && rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes)) ? 2 : 1;
+    }
 }
 // fused update launch of the variant in use (rlc_api_sac.hip / rlc_api_naf.hip)
 int rlc_h_sac_launch_update(rlc_handle* h, int first, int n, int n_updates, int source, const long long* idx_dev,
@@ -81,31 +144,43 @@ int rlc_h_sac_launch_update(rlc_handle* h, int first, int n, int n_updates, int 
 int rlc_h_naf_launch_update(rlc_handle* h, int first, int n, int n_updates, int source, const long long* idx_dev,
                             const struct RlcNafRollout* rollout);
 
-// re-pack the four per-agent blobs of an RlcSacDev handle between the row-major and the tile-blocked layout
-int rlc_h_sac_relayout(rlc_handle* h, int blocked);
-// bodies shared by the rlc_sac_* and rlc_kl_* entry points (rlc_api_sac.hip); algo = RLC_ALGO_SAC or RLC_ALGO_KL
-extern "C" {
-int rlc_sacfam_param_count(int algo, const rlc_handle* h, int64_t* out_p);
-int rlc_sacfam_set_blob(int algo, rlc_handle* h, int32_t agent, int32_t which, const float* src, int64_t n);
-int rlc_sacfam_get_blob(int algo, rlc_handle* h, int32_t agent, int32_t which, float* dst, int64_t n);
-int rlc_sacfam_init_target(int algo, rlc_handle* h, int32_t agent);
-int rlc_sacfam_act(int algo, rlc_handle* h, int32_t first_agent, int32_t n, const double* states, int32_t sample,
-                   const float* eps, float* out_actions);
-int rlc_sacfam_act_queue(int algo, rlc_handle* h, int32_t first_agent, int32_t n, const double* states, int32_t sample,
-                         const float* eps);
-int rlc_sacfam_act_fetch(int algo, rlc_handle* h, int32_t first_agent, int32_t n, float* out_actions);
-int rlc_sacfam_update(int algo, rlc_handle* h, int32_t n_updates, const int64_t* host_indices, const float* eps);
-int rlc_sacfam_update_batch(int algo, rlc_handle* h, int32_t agent, int32_t batch, const double* states,
-                            const double* actions, const double* next_states, const double* rewards,
-                            const double* gammas, const float* eps);
-int rlc_sacfam_enable_grad_taps(int algo, rlc_handle* h, int32_t on);
-int rlc_sacfam_last_tap(int algo, rlc_handle* h, int32_t agent, int32_t which, float* dst, int64_t n);
-}
+// bodies of the rlc_sac_* / rlc_kl_* entry points that carry eps (rlc_api_sac.hip); algo = RLC_ALGO_SAC or RLC_ALGO_KL
+int rlc_sacfam_act(int algo, rlc_handle* h, int first_agent, int n, const double* states, int sample, const float* eps,
+                   bool queued, float* out_actions);
+int rlc_sacfam_update(int algo, rlc_handle* h, int n_updates, const int64_t* host_indices, const float* eps);
+int rlc_sacfam_update_batch(int algo, rlc_handle* h, int agent, int batch, const double* states, const double* actions,
+                            const double* next_states, const double* rewards, const double* gammas, const float* eps);
 
-// shared helpers (rlc_api.hip)
+// ---- one body per operation for every algorithm (rlc_api.hip); `algo` is the one the calling entry point belongs to ----
 int rlc_h_check_agent(const rlc_handle* h, int agent);
 int rlc_h_use_device(const rlc_handle* h);
-// queued acting forward (rlc_api.hip): pinned staging + completion word
+int rlc_h_param_count(const rlc_handle* h, int algo, int64_t* out_p);
+int rlc_h_set_blob(rlc_handle* h, int algo, int agent, int which, const float* src, int64_t n);
+int rlc_h_get_blob(rlc_handle* h, int algo, int agent, int which, float* dst, int64_t n);
+int rlc_h_init_target(rlc_handle* h, int algo, int agent);
+int rlc_h_beta_powers(rlc_handle* h, int algo, int agent, float* pw, bool set);
+int rlc_h_enable_grad_taps(rlc_handle* h, int algo, int on);
+int rlc_h_last_tap(rlc_handle* h, int algo, int agent, int which, float* dst, int64_t n);
+// re-pack every blob between the row-major and the tile-blocked layout (a kernel switch changes the weight layout)
+int rlc_h_relayout(rlc_handle* h, int blocked);
+// set_kernel: argument checks (mfma_refusal: why variant 2 cannot run, empty if it can), then the re-pack
+int rlc_h_set_kernel(rlc_handle* h, int algo, int variant, const std::string& mfma_refusal, bool refuse_rollout = true);
+int rlc_h_get_kernel(const rlc_handle* h, int algo, int32_t* variant_in_use);
+// set_split, first half: handle / range / rollout checks; n_workgroups == 1 switches latency mode off
+int rlc_h_split_check(rlc_handle* h, int algo, int n_workgroups);
+// set_split, second half: `grid` co-resident workgroups must fit the GPU; barrier and error words; `part_floats` > 0:
+// a (new) zeroed partial-result buffer of that size; re-arm
+int rlc_h_split_arm(rlc_handle* h, int n_workgroups, int grid, size_t part_floats);
+// update, front half: checks, then the minibatch source and (host indices) their device-readable copy in *idx, with room
+// for extra_ll more 8-byte words behind them in h->idx_dev.  pinned_small: up to 1024 indices are read by the kernel
+// straight from pinned host memory (*idx == h->idx_pin; the caller then calls rlc_h_update_launched behind its launch)
+int rlc_h_update_begin(rlc_handle* h, int algo, int n_updates, const int64_t* host_indices, size_t extra_ll,
+                       bool pinned_small, int* source, const long long** idx);
+int rlc_h_update_launched(rlc_handle* h, const long long* idx);
+// update_batch, front half: checks, fp64 minibatch -> pinned staging -> the agent's gather slots
+int rlc_h_stage_batch(rlc_handle* h, int algo, int agent, int batch, const double* states, const double* actions,
+                      const double* next_states, const double* rewards, const double* gammas);
+// queued acting forward: pinned staging + completion word
 int rlc_h_aq_begin(rlc_handle* h, size_t floats, bool flagged);
 int* rlc_h_aq_flag(rlc_handle* h);
 int rlc_h_aq_wait(rlc_handle* h, int first_agent, int n);
@@ -124,3 +199,86 @@ int rlc_h_malloc(rlc_handle* h, T** out, size_t count, bool zero = true) {
     *out = (T*)p;
     return 0;
 }
+
+// Acting, both forms: agent-range check, fp64 states -> fp32 staging with `extra_f` more input floats behind them
+// (SoftActorCritic's eps), launch(inputs, outputs), and for the plain form the out_f output floats copied to `out` /
+// `out2` (the last out2_f of them; may be null).  queued: zero-copy through pinned memory, nothing is waited for.
+template <class L>
+int rlc_h_act(rlc_handle* h, int algo, int first_agent, int n, const double* states, const float* extra, size_t extra_f,
+              size_t out_f, bool queued, L launch, float* out = nullptr, float* out2 = nullptr, size_t out2_f = 0) {
+    RLC_NEED(h, algo);
+    if (rlc_h_use_device(h)) return 1;
+    RLC_REQUIRE(n >= 1 && first_agent >= 0 && first_agent + n <= h->rep.n_agents, "agent range [%d,%d) invalid",
+                first_agent, first_agent + n);
+    RLC_REQUIRE(states && (queued || out), "null array");
+    const size_t in_f = (size_t)n * h->rep.S + extra_f;
+    if (queued ? rlc_h_aq_begin(h, in_f + out_f, n == 1) : rlc_h_ensure_io(h, sizeof(float) * (in_f + out_f))) return 1;
+    float* hin = queued ? h->aq_host : (float*)h->io_host;
+    for (size_t i = 0; i < in_f - extra_f; i++) hin[i] = (float)states[i];
+    for (size_t i = 0; i < extra_f; i++) hin[in_f - extra_f + i] = extra[i];
+    if (queued) {
+        if (launch(hin, hin + in_f)) return 1;
+        h->aq_first = first_agent; h->aq_n = n;
+        h->aq_out = in_f;
+        return 0;
+    }
+    RLC_HIP(hipMemcpyAsync(h->io_dev, hin, sizeof(float) * in_f, hipMemcpyHostToDevice, h->st));
+    if (launch(h->io_dev, h->io_dev + in_f)) return 1;
+    RLC_HIP(hipMemcpyAsync(hin + in_f, h->io_dev + in_f, sizeof(float) * out_f, hipMemcpyDeviceToHost, h->st));
+    RLC_HIP(hipStreamSynchronize(h->st));
+    memcpy(out, hin + in_f, sizeof(float) * (out_f - out2_f));
+    if (out2) memcpy(out2, hin + in_f + out_f - out2_f, sizeof(float) * out2_f);
+    return 0;
+}
+// wait for the queued forward of agents [first_agent, first_agent + n) and copy its out_f output floats out
+int rlc_h_act_fetch(rlc_handle* h, int algo, int first_agent, int n, size_t out_f, float* out, float* out2 = nullptr,
+                    size_t out2_f = 0);
+
+// The skeleton of every rlc_*_create: the handle, device allocations and host -> device uploads on the handle's stream
+// (behind the zero-fill of their buffers); the first failure sticks and finish() reports it.
+struct RlcCreate {
+    rlc_handle* h;
+    int rc;
+    hipError_t e = hipSuccess;
+    std::vector<float> pw;
+    RlcCreate(int algo, int device, int n_agents, int S, int A, int B, long long cap, const uint64_t* seeds)
+        : h(new rlc_handle()) {
+        rc = rlc_h_init_common(h, algo, device, n_agents, S, A, B, cap, seeds);
+    }
+    template <typename T>
+    void alloc(T** out, size_t count, bool zero = true) {
+        if (!rc) rc = rlc_h_malloc(h, out, count, zero);
+    }
+    void up(void* dst, const void* src, size_t bytes) {
+        if (!rc && e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->st);
+    }
+    // a device copy of src[count]
+    template <typename T>
+    void upload(const T** out, const T* src, size_t count) {
+        T* p = nullptr;
+        alloc(&p, count);
+        up(p, src, count * sizeof(T));
+        *out = p;
+    }
+    // parameters, target, optimizer moments; Adam's beta powers start at beta1, beta2
+    template <class Dev>
+    void blobs(Dev& dv, bool beta_powers = true) {
+        const size_t NA = dv.n_agents, n = rlc_beta_powers(dv);
+        for (float** b : rlc_blobs(dv)) alloc(b, NA * dv.d.Ppad);
+        if (!beta_powers) return;
+        pw.resize(NA * n);
+        for (size_t i = 0; i < pw.size(); i++) pw[i] = i % 2 ? 0.999f : 0.9f;
+        alloc(&dv.pw, pw.size());
+        up(dv.pw, pw.data(), pw.size() * sizeof(float));
+    }
+    int finish(const char* who, rlc_handle** out) {
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(h->st);
+        if (!rc && e != hipSuccess) {
+            rlc_set_error("%s: upload failed: %s", who, hipGetErrorString(e));
+            rc = 1;
+        }
+        if (rc) rlc_h_destroy(h);
+        else *out = h;
+        return rc;
+    }
+};

@@ -1,13 +1,12 @@
 """Python face of a ReverseKL / ForwardKL population handle (rlc_kl_* in include/rlcontrol_hip.h)."""
 import ctypes
 import math
-from collections import OrderedDict
 
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr, f64, fptr, iptr
-from .hip_pop import Population
+from ._lib import check, fptr
+from .hip_pop import SampledPolicyPopulation, broadcast as bc, layout_of
 from .utils.quadrature import interior_action_nodes, sparse_grid_action_nodes
 
 KINDS = {"reverse": 1, "forward": 2}
@@ -18,16 +17,12 @@ Q_UPDATE_TYPES = {"non_sac": 0, "sac": 1}
 def param_layout(S, A, L1A, L2A, L1C, L2C):
     """name -> (offset, shape); modules pi_net, q_net, v_net (reversekl_network.py:47-50), weights [in, out]:
     the transpose of the nn.Linear.weight tensors of a state_dict."""
-    out, p = OrderedDict(), 0
-    for name, shp in (("pW1", (S, L1A)), ("pb1", (L1A,)), ("pW2", (L1A, L2A)), ("pb2", (L2A,)),
+    return layout_of((("pW1", (S, L1A)), ("pb1", (L1A,)), ("pW2", (L1A, L2A)), ("pb2", (L2A,)),
                       ("pWm", (L2A, A)), ("pbm", (A,)), ("pWs", (L2A, A)), ("pbs", (A,)),
                       ("qW1", (S + A, L1C)), ("qb1", (L1C,)), ("qW2", (L1C, L2C)), ("qb2", (L2C,)),
                       ("qW3", (L2C, 1)), ("qb3", (1,)),
                       ("vW1", (S, L1C)), ("vb1", (L1C,)), ("vW2", (L1C, L2C)), ("vb2", (L2C,)),
-                      ("vW3", (L2C, 1)), ("vb3", (1,))):
-        out[name] = (p, shp)
-        p += int(np.prod(shp))
-    return out, p
+                      ("vW3", (L2C, 1)), ("vb3", (1,))))
 
 
 def init_params(S, A, L1A, L2A, L1C, L2C, seed):
@@ -48,8 +43,8 @@ def init_params(S, A, L1A, L2A, L1C, L2C, seed):
     return th
 
 
-class KLPopulation(Population):
-    BLOB = {"theta": 0, "theta_target": 1, "adam_m": 2, "adam_v": 3}
+class KLPopulation(SampledPolicyPopulation):
+    PREFIX = "rlc_kl"
     TAP = {"q": 0, "v": 1, "logp": 2, "q_pi": 3, "loss": 4, "grads": 5, "intgrl_q": 6}
 
     def __init__(self, kind, n_agents, state_dim, action_dim, actor_l1_dim, actor_l2_dim, critic_l1_dim, critic_l2_dim,
@@ -80,9 +75,9 @@ class KLPopulation(Population):
         if node_a.size != node_w.size * self.A:
             raise ValueError("nodes: actions [K, action_dim] and weights [K] differ in length")
         self.n_nodes = int(node_w.size)
-        bc = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (self.n_agents,)))
-        self._keep = dict(lp=bc(pi_lr), lq=bc(qf_vf_lr), al=bc(entropy_scale), na=node_a, nw=node_w,
-                          seed=np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64).reshape(-1), (self.n_agents,))))
+        self._keep = dict(lp=bc(pi_lr, self.n_agents), lq=bc(qf_vf_lr, self.n_agents), al=bc(entropy_scale, self.n_agents),
+                          na=node_a, nw=node_w)
+        self._keep["seed"], seed_ptr = self._seeds(seeds)
         cfg = _lib.rlc_kl_config()
         cfg.device, cfg.n_agents, cfg.state_dim, cfg.action_dim = int(device), self.n_agents, self.S, self.A
         cfg.actor_l1_dim, cfg.actor_l2_dim, cfg.critic_l1_dim, cfg.critic_l2_dim = self.dims[2:]
@@ -92,29 +87,8 @@ class KLPopulation(Population):
         cfg.tau, cfg.action_max0 = float(tau), float(action_max0)
         cfg.node_actions, cfg.node_weights = fptr(node_a), fptr(node_w)
         cfg.pi_lr, cfg.qf_vf_lr, cfg.entropy_scale = fptr(self._keep["lp"]), fptr(self._keep["lq"]), fptr(self._keep["al"])
-        cfg.seed = self._keep["seed"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        cfg.seed = seed_ptr
         check(self._lib.rlc_kl_create(ctypes.byref(cfg), ctypes.byref(self._h)))
-
-    def set_blob(self, agent, which, values):
-        v = np.ascontiguousarray(values, np.float32).reshape(-1)
-        check(self._lib.rlc_kl_set_blob(self._h, int(agent), self.BLOB[which], fptr(v), ctypes.c_int64(v.size)))
-
-    def get_blob(self, agent, which):
-        out = np.empty(self.P, np.float32)
-        check(self._lib.rlc_kl_get_blob(self._h, int(agent), self.BLOB[which], fptr(out), ctypes.c_int64(self.P)))
-        return out
-
-    def set_params(self, agent, theta, init_target=True):
-        self.set_blob(agent, "theta", theta)
-        if init_target:
-            check(self._lib.rlc_kl_init_target(self._h, int(agent)))
-
-    def debug_fail_next_split(self):
-        check(self._lib.rlc_debug_fail_next_split(self._h))
-
-    def set_split(self, n_workgroups):
-        """latency mode: the node passes of each agent's action integral over that many CUs (1 = off)"""
-        check(self._lib.rlc_kl_set_split(self._h, ctypes.c_int32(int(n_workgroups))))
 
     def get_step(self, agent):
         out = ctypes.c_int32(0)
@@ -124,66 +98,6 @@ class KLPopulation(Population):
     def set_step(self, agent, step):
         check(self._lib.rlc_kl_set_step(self._h, int(agent), ctypes.c_int32(int(step))))
 
-    def act(self, states, first_agent=0, sample=False, eps=None):
-        s = f64(states).reshape(-1, self.S)
-        out = np.empty((s.shape[0], self.A), np.float32)
-        e = None if eps is None else np.ascontiguousarray(eps, np.float32).reshape(s.shape[0], self.A)
-        check(self._lib.rlc_kl_act(self._h, int(first_agent), ctypes.c_int32(s.shape[0]), dptr(s),
-                                   ctypes.c_int32(1 if sample else 0), fptr(e) if e is not None else None, fptr(out)))
-        return out
-
-    def act_queue(self, states, first_agent=0, sample=False, eps=None):
-        """queue the acting forward for `states` behind the work already on the handle's stream (no synchronisation)"""
-        s = f64(states).reshape(-1, self.S)
-        e = None if eps is None else np.ascontiguousarray(eps, np.float32).reshape(s.shape[0], self.A)
-        check(self._lib.rlc_kl_act_queue(self._h, int(first_agent), ctypes.c_int32(s.shape[0]), dptr(s),
-                                          ctypes.c_int32(1 if sample else 0), fptr(e) if e is not None else None))
-        return s.shape[0]
-
-    def act_fetch(self, n, first_agent=0):
-        out = np.empty((int(n), self.A), np.float32)
-        check(self._lib.rlc_kl_act_fetch(self._h, int(first_agent), ctypes.c_int32(int(n)), fptr(out)))
-        return out
-
-    def update(self, n_updates=1, host_indices=None, eps=None):
-        idx = None
-        if host_indices is not None:
-            idx = np.ascontiguousarray(host_indices, np.int64)
-            if idx.size != self.n_agents * int(n_updates) * self.B:
-                raise ValueError("host_indices must hold n_agents*n_updates*batch_size entries")
-        e = None
-        if eps is not None:
-            e = np.ascontiguousarray(eps, np.float32)
-            if e.size != self.n_agents * int(n_updates) * self.B * self.A:
-                raise ValueError("eps must hold n_agents*n_updates*batch_size*action_dim entries")
-        check(self._lib.rlc_kl_update(self._h, ctypes.c_int32(int(n_updates)), iptr(idx) if idx is not None else None,
-                                      fptr(e) if e is not None else None))
-
-    def update_batch(self, agent, states, actions, next_states, rewards, gammas, eps=None):
-        r = f64(rewards).reshape(-1)
-        n = r.size
-        s, s2 = f64(states).reshape(n, self.S), f64(next_states).reshape(n, self.S)
-        a, g = f64(actions).reshape(n, self.A), f64(gammas).reshape(n)
-        e = None if eps is None else np.ascontiguousarray(eps, np.float32).reshape(n, self.A)
-        check(self._lib.rlc_kl_update_batch(self._h, int(agent), ctypes.c_int32(n), dptr(s), dptr(a), dptr(s2), dptr(r),
-                                            dptr(g), fptr(e) if e is not None else None))
-
-    KERNEL = {"auto": 0, "generic": 1, "mfma": 2}
-
-    def set_kernel(self, name):
-        check(self._lib.rlc_kl_set_kernel(self._h, self.KERNEL[name]))
-
-    def kernel_in_use(self):
-        out = ctypes.c_int32(0)
-        check(self._lib.rlc_kl_get_kernel(self._h, ctypes.byref(out)))
-        return {v: k for k, v in self.KERNEL.items()}[out.value]
-
-    def enable_grad_taps(self, on=True):
-        check(self._lib.rlc_kl_enable_grad_taps(self._h, 1 if on else 0))
-
-    def last_tap(self, agent, which):
-        n = {"q": self.B, "v": self.B, "logp": self.B, "q_pi": self.B, "loss": 3, "grads": self.P,
-             "intgrl_q": self.B * self.n_nodes}[which]
-        out = np.empty(n, np.float32)
-        check(self._lib.rlc_kl_last_tap(self._h, int(agent), self.TAP[which], fptr(out), ctypes.c_int64(n)))
-        return out
+    def tap_lengths(self):
+        return {"q": self.B, "v": self.B, "logp": self.B, "q_pi": self.B, "loss": 3, "grads": self.P,
+                "intgrl_q": self.B * self.n_nodes}

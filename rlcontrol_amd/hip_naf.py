@@ -1,15 +1,11 @@
 """Python face of a NAF population handle (rlc_naf_* in include/rlcontrol_hip.h)."""
 import ctypes
-from collections import OrderedDict
 
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr, f64, fptr, iptr
-from .hip_pop import Population
-
-
-NORM_TYPES = {"none": 0, "input_norm": 0, "layer": 1}
+from ._lib import check, dptr, f64, fptr
+from .hip_pop import NORM_TYPES, Population, broadcast as bc, layout_of
 
 
 def param_layout(S, A, L1, L2, norm_type="input_norm"):
@@ -26,11 +22,7 @@ def param_layout(S, A, L1, L2, norm_type="input_norm"):
         segs += [("Wd%d" % c, (L1, 1)), ("bd%d" % c, (1,))]
     for c in range(A - 1):
         segs += [("Wn%d" % c, (L1, A - 1 - c)), ("bn%d" % c, (A - 1 - c,))]
-    out, p = OrderedDict(), 0
-    for name, shp in segs:
-        out[name] = (p, shp)
-        p += int(np.prod(shp))
-    return out, p
+    return layout_of(segs)
 
 
 def init_params(S, A, L1, L2, seed, norm_type="input_norm"):
@@ -54,6 +46,8 @@ def init_params(S, A, L1, L2, seed, norm_type="input_norm"):
 
 
 class NAFPopulation(Population):
+    PREFIX = "rlc_naf"
+    BETA_POWERS = 2
     BLOB = {"theta": 0, "theta_target": 1, "adam_m": 2, "adam_v": 3}
     TAP = {"q": 0, "y": 1, "V": 2, "grads": 3}
 
@@ -64,10 +58,9 @@ class NAFPopulation(Population):
         self.dims = (self.S, self.A, int(l1_dim), int(l2_dim))
         self.norm_type = norm_type
         self.layout, self.P = param_layout(*self.dims, norm_type=norm_type)
-        bc = lambda v, n: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (n,)))
         self._keep = dict(smin=bc(state_min, self.S), smax=bc(state_max, self.S), amax=bc(action_max, self.A),
-                          lr=bc(learning_rate, self.n_agents),
-                          seed=np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64).reshape(-1), (self.n_agents,))))
+                          lr=bc(learning_rate, self.n_agents))
+        self._keep["seed"], seed_ptr = self._seeds(seeds)
         cfg = _lib.rlc_naf_config()
         cfg.device, cfg.n_agents, cfg.state_dim, cfg.action_dim = int(device), self.n_agents, self.S, self.A
         cfg.l1_dim, cfg.l2_dim = self.dims[2:]
@@ -78,27 +71,8 @@ class NAFPopulation(Population):
         self._keep["amin"] = bc(-np.asarray(self._keep["amax"]) if action_min is None else action_min, self.A)
         cfg.action_min = fptr(self._keep["amin"])
         cfg.learning_rate = fptr(self._keep["lr"])
-        cfg.seed = self._keep["seed"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        cfg.seed = seed_ptr
         check(self._lib.rlc_naf_create(ctypes.byref(cfg), ctypes.byref(self._h)))
-
-    def set_blob(self, agent, which, values):
-        v = np.ascontiguousarray(values, np.float32).reshape(-1)
-        check(self._lib.rlc_naf_set_blob(self._h, int(agent), self.BLOB[which], fptr(v), ctypes.c_int64(v.size)))
-
-    def get_blob(self, agent, which):
-        out = np.empty(self.P, np.float32)
-        check(self._lib.rlc_naf_get_blob(self._h, int(agent), self.BLOB[which], fptr(out), ctypes.c_int64(self.P)))
-        return out
-
-    def set_params(self, agent, theta, init_target=True):
-        self.set_blob(agent, "theta", theta)
-        if init_target:
-            check(self._lib.rlc_naf_init_target(self._h, int(agent)))
-
-    def get_beta_powers(self, agent):
-        out = np.empty(2, np.float32)
-        check(self._lib.rlc_naf_get_beta_powers(self._h, int(agent), fptr(out)))
-        return out
 
     def act(self, states, first_agent=0, with_lcols=False):
         s = f64(states).reshape(-1, self.S)
@@ -108,49 +82,11 @@ class NAFPopulation(Population):
                                     fptr(lc) if lc is not None else None))
         return (mu, lc) if with_lcols else mu
 
-    def act_queue(self, states, first_agent=0):
-        """queue the greedy forward (mu and the L columns) for `states` behind the work already on the handle's stream"""
-        s = f64(states).reshape(-1, self.S)
-        check(self._lib.rlc_naf_act_queue(self._h, int(first_agent), ctypes.c_int32(s.shape[0]), dptr(s)))
-        return s.shape[0]
-
     def act_fetch(self, n, first_agent=0):
         mu = np.empty((int(n), self.A), np.float32)
         lc = np.empty((int(n), self.A * (self.A + 1) // 2), np.float32)
         check(self._lib.rlc_naf_act_fetch(self._h, int(first_agent), ctypes.c_int32(int(n)), fptr(mu), fptr(lc)))
         return mu, lc
 
-    def update(self, n_updates=1, host_indices=None):
-        idx = None
-        if host_indices is not None:
-            idx = np.ascontiguousarray(host_indices, np.int64)
-            if idx.size != self.n_agents * int(n_updates) * self.B:
-                raise ValueError("host_indices must hold n_agents*n_updates*batch_size entries")
-        check(self._lib.rlc_naf_update(self._h, ctypes.c_int32(int(n_updates)), iptr(idx) if idx is not None else None))
-
-    def update_batch(self, agent, states, actions, next_states, rewards, gammas):
-        r = f64(rewards).reshape(-1)
-        n = r.size
-        s, s2 = f64(states).reshape(n, self.S), f64(next_states).reshape(n, self.S)
-        a, g = f64(actions).reshape(n, self.A), f64(gammas).reshape(n)
-        check(self._lib.rlc_naf_update_batch(self._h, int(agent), ctypes.c_int32(n), dptr(s), dptr(a), dptr(s2), dptr(r),
-                                             dptr(g)))
-
-    KERNEL = {"auto": 0, "generic": 1, "mfma": 2}
-
-    def set_kernel(self, name):
-        check(self._lib.rlc_naf_set_kernel(self._h, self.KERNEL[name]))
-
-    def kernel_in_use(self):
-        out = ctypes.c_int32(0)
-        check(self._lib.rlc_naf_get_kernel(self._h, ctypes.byref(out)))
-        return {v: k for k, v in self.KERNEL.items()}[out.value]
-
-    def enable_grad_taps(self, on=True):
-        check(self._lib.rlc_naf_enable_grad_taps(self._h, 1 if on else 0))
-
-    def last_tap(self, agent, which):
-        n = {"q": self.B, "y": self.B, "V": self.B, "grads": self.P}[which]
-        out = np.empty(n, np.float32)
-        check(self._lib.rlc_naf_last_tap(self._h, int(agent), self.TAP[which], fptr(out), ctypes.c_int64(n)))
-        return out
+    def tap_lengths(self):
+        return {"q": self.B, "y": self.B, "V": self.B, "grads": self.P}
