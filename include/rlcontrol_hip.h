@@ -144,12 +144,17 @@ int rlc_ddpg_qval(rlc_ddpg* h, int32_t agent, int32_t n, const double* states, c
 int rlc_ddpg_update(rlc_ddpg* h, int32_t n_updates, const int64_t* host_indices);
 int rlc_ddpg_update_batch(rlc_ddpg* h, int32_t agent, int32_t batch, const double* states, const double* actions,
                           const double* next_states, const double* rewards, const double* gammas);
-/* kernel selection for A/B tests: 0 auto, 1 generic (any dims), 2 MFMA-tiled (gfx950 fp32 matrix cores) */
+/* kernel selection: 0 auto, 1 generic (any dims), 2 MFMA-tiled (gfx950 fp32 matrix cores).
+ *  0 chooses the MFMA kernel at state_dim <= 8, action_dim <= 2 (no layer norm, layer widths multiples of 4 in
+ *  [16, 256], batch_size <= 128, LDS <= 160 KiB) and the generic kernel everywhere else.  2 also takes the wide shapes
+ *  -- state_dim <= 32, action_dim in {1, 2, 3, 4, 6}, the other limits as above -- which run on request only; a refusal
+ *  reads "MFMA kernel does not support these dimensions: <the limit exceeded>" (the LDS limit with the bytes needed and
+ *  allowed).  Either switch re-packs weights and optimizer state; acting, qval and the replay work in both layouts. */
 int rlc_ddpg_set_kernel(rlc_ddpg* h, int32_t variant);
 int rlc_ddpg_get_kernel(const rlc_ddpg* h, int32_t* variant_in_use);
 /* latency mode (no reference counterpart): split every agent's minibatch over n_workgroups CUs (1 = off, at most 8;
- * MFMA shapes only; n_agents rounded up to 8, times n_workgroups, must not exceed the CU count, and nothing else may
- * occupy the GPU while an update runs: the workgroups of an agent meet at four barriers per update).  Results equal the
+ * MFMA kernel at state_dim <= 8, action_dim <= 2 only; n_agents rounded up to 8, times n_workgroups, must not exceed
+ * the CU count, and nothing else may occupy the GPU while an update runs: the workgroups of an agent meet at four barriers per update).  Results equal the
  * one-workgroup kernel up to the summation order over the batch. */
 int rlc_ddpg_set_split(rlc_ddpg* h, int32_t n_workgroups);
 /* Failure behaviour of latency mode (DDPG and KL): when a cross-workgroup barrier does not complete (a peer workgroup

@@ -16,10 +16,13 @@ OBJ = os.path.join(CSRC, ("_obj_stamps" if STAMPS else "_obj") + ("_fast" if os.
 OUT = os.path.join(_HERE, "librlcontrol_hip_stamps.so" if STAMPS else "librlcontrol_hip.so")
 PLAIN = ("rlc_api.hip", "rlc_api_sac.hip", "rlc_api_naf.hip", "replay_kernels.hip", "ddpg_generic.hip", "ddpg_mfma.hip", "sac_generic.hip", "sac_mfma.hip", "naf_generic.hip", "naf_mfma.hip", "rollout_kernels.hip", "rlc_api_rollout.hip", "kl_generic.hip", "rlc_api_kl.hip", "ddpg_split.hip", "kl_mfma.hip", "kl_mfma_a2.hip")
 MFMA_VARIANTS = [(mt, ad) for ad in (1, 2) for mt in (2, 4, 7, 8)]
+# the wide form of the DDPG kernel (state_dim <= 32, action_dim in {1,2,3,4,6}; ddpg_mfma_kernel.h, WIDE): no tail-of-four units
+MFMA_WIDE_VARIANTS = [(mt, ad) for ad in (1, 2, 3, 4, 6) for mt in (2, 4, 7, 8)]
 FAST = os.environ.get("RLC_FAST_BUILD", "0") == "1"     # developer loop: only the headline shape
 SAC_VARIANTS = [(mt, ntw, ad) for ad in (1, 2) for ntw in (1, 2) for mt in (2, 4, 7, 8)]
 if FAST:
     MFMA_VARIANTS = [(7, 1)]
+    MFMA_WIDE_VARIANTS = []
     SAC_VARIANTS = [(7, 1, 1)]
 SPLIT_VARIANTS = [(2, 1)] if FAST else [(mt, ad) for ad in (1, 2) for mt in (1, 2, 4)]
 NAF_VARIANTS = [(7, 2, 2)] if FAST else [(mt, ntw, ad) for ad in (1, 2) for ntw in (1, 2) for mt in (2, 4, 7, 8)]
@@ -51,6 +54,9 @@ def _units():
         for flag, tag in t4(mt):
             units.append((os.path.join(CSRC, "ddpg_mfma_inst.hip"), os.path.join(OBJ, "ddpg_mfma_%d_%d%s.o" % (mt, ad, tag)),
                           ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad, "-DRLC_T4=%d" % flag]))
+    for mt, ad in MFMA_WIDE_VARIANTS:
+        units.append((os.path.join(CSRC, "ddpg_mfma_inst.hip"), os.path.join(OBJ, "ddpg_mfma_w_%d_%d.o" % (mt, ad)),
+                      ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad, "-DRLC_WIDE=1"]))
     for mt, ad in SPLIT_VARIANTS:
         units.append((os.path.join(CSRC, "ddpg_split_inst.hip"), os.path.join(OBJ, "ddpg_split_%d_%d.o" % (mt, ad)),
                       ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad]))
@@ -68,7 +74,8 @@ def _units():
 _LLVM = "/opt/rocm/lib/llvm/bin"
 # Units whose kernels must not carry whole-wave spills (see audit_object); the MFMA kernels are reported, not refused:
 # their SGPR spills sit at phase boundaries and they run two waves per SIMD with the full 256-register budget.
-GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o")
+GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o") + tuple(
+    "ddpg_mfma_w_%d_%d.o" % v for v in MFMA_WIDE_VARIANTS)      # the wide DDPG units are held to the same policy
 USAGE_JSON = os.path.join(_HERE, "kernel_resource_usage.json")
 
 

@@ -5,7 +5,8 @@
 // contractions of one update run on the MFMA building blocks of mfma_blocks.h and nothing [B,H]-sized ever
 // leaves the CU (see that header for the LDS / VGPR / HBM roles and the tiling).
 //
-// Supported shapes: S <= 8, A in {1,2}, H1/HA/HC multiples of 4 in [16,256], B <= 128.
+// Supported shapes: S <= 8, A in {1,2}, H1/HA/HC multiples of 4 in [16,256], B <= 128; in the WIDE form (opt-in through
+// rlc_ddpg_set_kernel, see rlc_mfma_wide) S <= 32 and A in {1,2,3,4,6}.
 #pragma once
 #include "mfma_blocks.h"
 #include "ddpg_rollout_device.h"
@@ -33,7 +34,16 @@ struct Smem {
     lds_f32 *w1t, *w1o; // first layer staged in LDS ([S][H1] weights, [H1] biases): target / online (mfma_blocks.h stage_*)
 };
 
+// shapes that only the WIDE form of the kernel takes: a state row above SMAX floats or more than two action columns
+__host__ __device__ inline bool rlc_mfma_wide(const RlcDims& d) { return d.S > SMAX || d.A > 2; }
+
 // carve the dynamic LDS; base may be null (host: only the size is wanted)
+// The WIDE form (rlc_mfma_wide(d)) keeps its state rows at stride xld_for(S) and saves what its wider per-sample
+// arrays cost elsewhere: `part` lies in the mask bytes (the kernel stores a phase's masks only once the partials in
+// front of them have been summed), `dz` in `a` (dead once the critic has stepped), and the split-tile hand-off exists
+// only where a layer has the 13 tiles that split.  (A template argument, not a test of d: the narrow kernels' carve is
+// the straight-line code it was.)
+template <bool WIDE = false>
 __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* base, Smem* out) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -42,6 +52,8 @@ __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* b
         return p;
     };
     const int MB = MT * 16, A = d.A, LDH = ldh_for(d.H1);
+    constexpr bool wide = WIDE;
+    const int XL = wide ? xld_for(d.S) : SMAX;
     Smem L;
     // + 16 floats of tail: the unmasked fragment reads of the last k-chunk run up to 15 floats past a row's
     // end (into the next row, or into this zeroed tail after the last row)
@@ -50,20 +62,29 @@ __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* b
     L.g = (lds_f64*)take(sizeof(double) * MB);
     L.idx = (lds_i64*)take(sizeof(long long) * RLC_MAX_BATCH);
     L.mask = take((size_t)MB * MSTRIDE);
-    L.part = (lds_f32*)take(sizeof(float) * kWaves * MB * A);
+    static_assert(sizeof(float) * kWaves * 6 <= MSTRIDE, "the WIDE form's partials fit the mask rows");
+    if constexpr (wide) L.part = (lds_f32*)L.mask;
+    else L.part = (lds_f32*)take(sizeof(float) * kWaves * MB * A);
     L.wvec = (lds_f32*)take(sizeof(float) * A * 256);
-    L.x = (lds_f32*)take(sizeof(float) * MB * SMAX);      // rows padded to 8 floats: two ds_read_b128
-    L.x2 = (lds_f32*)take(sizeof(float) * MB * SMAX);
+    L.x = (lds_f32*)take(sizeof(float) * MB * XL);        // rows padded to 8 floats: two ds_read_b128
+    L.x2 = (lds_f32*)take(sizeof(float) * MB * XL);
     L.a = (lds_f32*)take(sizeof(float) * MB * A);
     L.aout = (lds_f32*)take(sizeof(float) * MB * A);
     L.mu = (lds_f32*)take(sizeof(float) * MB * A);
-    L.dz = (lds_f32*)take(sizeof(float) * MB * A);
+    if constexpr (wide) L.dz = L.a;
+    else L.dz = (lds_f32*)take(sizeof(float) * MB * A);
     L.q = (lds_f32*)take(sizeof(float) * MB);
     L.y = (lds_f32*)take(sizeof(float) * MB);
     L.dq = (lds_f32*)take(sizeof(float) * MB);
     L.pool = (lds_i32*)take(sizeof(int) * 3 * RLC_MAX_BATCH);
     L.dups = (lds_i32*)take(sizeof(int) * 4);
-    L.xbuf = (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4));
+    if constexpr (wide) {
+        auto t13 = [](int n) { return (n + 15) >> 4 == 13; };
+        if (t13(d.H1) || t13(d.HA) || t13(d.HC)) L.xbuf = (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4));
+        else L.xbuf = nullptr;
+    } else {
+        L.xbuf = (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4));
+    }
 #ifdef RLC_W1_STAGE
     L.w1t = (lds_f32*)take(sizeof(float) * (d.S + 1) * d.H1);
     L.w1o = (lds_f32*)take(sizeof(float) * (d.S + 1) * d.H1);
@@ -77,20 +98,28 @@ __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* b
 // FUSE: the actor's and the critic's second layers have one width: their hidden contractions over one trunk image run
 // as ONE k-loop (target pair, online pair)
 // T4: the minibatch ends within the first four rows of its last tile (mfma_blocks.h, Blk's T4; the launcher checks it)
-template <int MT, int AD, bool FUSE, bool T4>
+// WIDE: the form for rlc_mfma_wide shapes (Blk's WIDE first-layer passes, the carve above); the narrow instantiations
+// hold none of its code
+template <int MT, int AD, bool FUSE, bool T4, bool WIDE = false>
 __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev dv, int first_agent, int n_updates,
                                                                         int source, const long long* host_idx,
                                                                         int grad_taps, const RlcRollout* rollout,
                                                                         int q8_first) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using U = Blk<MT, NTW, MSTRIDE, false, false, T4>;
+    using U = Blk<MT, NTW, MSTRIDE, false, false, T4, WIDE>;
+    static_assert(WIDE || AD <= 2, "more than two action columns: the WIDE form");
+    static_assert(!(WIDE && T4), "the WIDE form has no tail-of-four units");
+#ifdef RLC_W1_STAGE
+    static_assert(!WIDE, "the staged first layer is sized for SMAX state rows");
+#endif
     constexpr int MB = U::MB;
     const RlcDims d = dv.d;
     U u;
     u.init_geometry();
     u.S = d.S; u.H1 = d.H1; u.B = d.B; u.LDH = ldh_for(d.H1);
+    const int XL = WIDE ? xld_for(d.S) : SMAX;       // floats between state rows in LDS
     Smem L;
-    smem_carve(d, MT, (lds_u8*)smem, &L);
+    smem_carve<WIDE>(d, MT, (lds_u8*)smem, &L);
     u.L.hbuf = L.hbuf; u.L.mask = L.mask; u.L.xbuf = L.xbuf;
     const int tid = u.tid, S = d.S, H1 = d.H1, HA = d.HA, HC = d.HC, B = d.B;
     const int agent = first_agent + blockIdx.x;
@@ -122,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
 
     // zero the padded tails of the per-sample vectors once (rows >= B never change afterwards)
     for (int i = tid; i < MB * AD; i += kThreads) { L.a[i] = 0.f; L.aout[i] = 0.f; L.mu[i] = 0.f; L.dz[i] = 0.f; }
-    for (int i = tid; i < MB * SMAX; i += kThreads) { L.x[i] = 0.f; L.x2[i] = 0.f; }
+    for (int i = tid; i < MB * XL; i += kThreads) { L.x[i] = 0.f; L.x2[i] = 0.f; }
     for (int i = tid; i < MB; i += kThreads) { L.q[i] = 0.f; L.y[i] = 0.f; L.dq[i] = 0.f; }
     for (int i = tid; i < MB * MSTRIDE / 4; i += kThreads) reinterpret_cast<lds_u32*>(L.mask)[i] = 0u;
     if (tid < 16) L.hbuf[MB * u.LDH + tid] = 0.0f;
@@ -195,8 +224,8 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
                 L.r[b] = ld_gather(&dv.rep.rr[slot]); L.g[b] = ld_gather(&dv.rep.rg[slot]);
             }
             for (int i = 0; i < S; i++) {
-                L.x[b * SMAX + i] = clip_state_val(ld_gather(&ps[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
-                L.x2[b * SMAX + i] = clip_state_val(ld_gather(&ps2[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x[b * XL + i] = clip_state_val(ld_gather(&ps[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x2[b * XL + i] = clip_state_val(ld_gather(&ps2[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
             }
 #pragma unroll
             for (int j = 0; j < AD; j++) L.a[b * AD + j] = ld_gather(&pa[j]);
@@ -390,7 +419,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         else u.fwd_gemm(acc, th + d.oWa2, HA, H1);
         u.template bias_relu<0>(acc, th + d.oba2, HA);
         u.template row_dot<false, AD>(acc, HA, [&](int n, int j) { return th[d.oWa3 + n * AD + j]; }, L.part);   // z partials
-        u.template store_masks<-2, true>(acc, HA);
+        if constexpr (!WIDE) u.template store_masks<-2, true>(acc, HA);      // (WIDE: the partials lie in the mask bytes)
         lds_barrier();
         STAMP();
         for (int i = tid; i < B * AD; i += kThreads) {
@@ -440,6 +469,8 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         STAMP();
 
         // ================= step 6: actor step =================
+        // WIDE: the last partials have been summed, the mask bytes are free for the actor's hidden layer now
+        if constexpr (WIDE) u.template store_masks<-2, true>(h2acc, HA);
         float g_wa3[NTW][AD], g_ba2[NTW];
         {
             const int NT = (HA + 15) >> 4;
@@ -473,6 +504,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             }
         }
         const float alpha_a = adam_alpha(lr_a, pw[0], pw[1]);
+        if constexpr (WIDE) lds_barrier();      // the masks stored above
         u.template bwd_gemm<AD, -2>(acc, th + d.oWa2, HA, H1, L.dz, L.wvec);
         lds_barrier();
         if (sep) {
@@ -493,19 +525,39 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             for (int i = 0; i < NTW; i++) {
                 const int t = u.tile_of(i);
                 const int n = 16 * t + u.c;
-                if (t < NT && n < HA && u.g <= AD) {
-                    // lane group 0 -> ba2[n]; groups 1..AD -> Wa3[n][j]
-                    int p = d.oba2 + n;
-                    float gr = g_ba2[i];
+                // Two bodies on purpose: up to three action columns the block is, token for token, the code the narrow
+                // instantiations have always had (their registers and spills stay what they were); above that a lane
+                // group takes two slots.
+                if constexpr (AD <= 3) {
+                    if (t < NT && n < HA && u.g <= AD) {
+                        // lane group 0 -> ba2[n]; groups 1..AD -> Wa3[n][j]
+                        int p = d.oba2 + n;
+                        float gr = g_ba2[i];
 #pragma unroll
-                    for (int j = 0; j < AD; j++)
-                        if (u.g == j + 1) { p = d.oWa3 + n * AD + j; gr = g_wa3[i][j]; }
-                    float mm = m_a[p], vv = v_a[p];
-                    const float o = tt[p];              // (with the other loads: one memory round trip, not two)
-                    const float nv = adam_step(th[p], gr, mm, vv, alpha_a);
-                    m_a[p] = mm; v_a[p] = vv; th[p] = nv;
-                    if (tap_ga) tap_ga[p] = gr;
-                    tt[p] = o + tau * (nv - o);
+                        for (int j = 0; j < AD; j++)
+                            if (u.g == j + 1) { p = d.oWa3 + n * AD + j; gr = g_wa3[i][j]; }
+                        float mm = m_a[p], vv = v_a[p];
+                        const float o = tt[p];              // (with the other loads: one memory round trip, not two)
+                        const float nv = adam_step(th[p], gr, mm, vv, alpha_a);
+                        m_a[p] = mm; v_a[p] = vv; th[p] = nv;
+                        if (tap_ga) tap_ga[p] = gr;
+                        tt[p] = o + tau * (nv - o);
+                    }
+                } else {
+                    // more slots (ba2[n], Wa3[n][0..AD-1]) than lane groups: group g takes the slots g and g + 4
+                    for (int s = u.g; s <= AD && t < NT && n < HA; s += 4) {
+                        int p = d.oba2 + n;
+                        float gr = g_ba2[i];
+#pragma unroll
+                        for (int j = 0; j < AD; j++)
+                            if (s == j + 1) { p = d.oWa3 + n * AD + j; gr = g_wa3[i][j]; }
+                        float mm = m_a[p], vv = v_a[p];
+                        const float o = tt[p];
+                        const float nv = adam_step(th[p], gr, mm, vv, alpha_a);
+                        m_a[p] = mm; v_a[p] = vv; th[p] = nv;
+                        if (tap_ga) tap_ga[p] = gr;
+                        tt[p] = o + tau * (nv - o);
+                    }
                 }
             }
             if (u.wave < AD) {            // ba3[j]: sum_b dz[b][j], wave j
@@ -538,13 +590,15 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
 #endif
 }
 
-template <int MT, int AD, bool FUSE, bool T4>
+template <int MT, int AD, bool FUSE, bool T4, bool WIDE>
 int launch_tf(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
               int grad_taps, hipStream_t st, const RlcRollout* rollout, int q8_first) {
-    const size_t lds = smem_carve(dv.d, MT, nullptr, nullptr);
+    const size_t lds = smem_carve<WIDE>(dv.d, MT, nullptr, nullptr);
     RLC_REQUIRE(lds <= 160 * 1024, "MFMA DDPG kernel needs %zu B of LDS (> 160 KiB)", lds);
     RLC_REQUIRE(!T4 || rlc_tail4(dv.d.B, MT), "tail-of-four kernel launched for batch %d", dv.d.B);
-    auto kern = rlc_ddpg_update_mfma_kernel<MT, AD, FUSE, T4>;
+    RLC_REQUIRE(WIDE == rlc_mfma_wide(dv.d), "state_dim %d / action_dim %d on the %s form of the MFMA kernel", dv.d.S, dv.d.A,
+                WIDE ? "wide" : "narrow");
+    auto kern = rlc_ddpg_update_mfma_kernel<MT, AD, FUSE, T4, WIDE>;
     static bool attr_set = false;
     if (!attr_set) {
         RLC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -556,14 +610,14 @@ int launch_tf(const RlcDev& dv, int first_agent, int n_agents, int n_updates, in
     return 0;
 }
 
-template <int MT, int AD, bool T4>
+template <int MT, int AD, bool T4, bool WIDE = false>
 int launch_t(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
              int grad_taps, hipStream_t st, const RlcRollout* rollout, int q8_first) {
 #ifndef RLC_DDPG_SEPARATE_FWD
     if (dv.d.HA == dv.d.HC && !dv.d.sep)
-        return launch_tf<MT, AD, true, T4>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
+        return launch_tf<MT, AD, true, T4, WIDE>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
 #endif
-    return launch_tf<MT, AD, false, T4>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
+    return launch_tf<MT, AD, false, T4, WIDE>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
 }
 
 }  // namespace

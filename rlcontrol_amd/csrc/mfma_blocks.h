@@ -90,6 +90,9 @@ __device__ __forceinline__ void lds_barrier() {
 constexpr int kThreads = 512;
 constexpr int kWaves = 8;     // two waves per SIMD: one can issue MFMA while the other does VALU / waits on loads
 constexpr int SMAX = 8;       // state rows are padded to 8 floats in LDS (two ds_read_b128)
+constexpr int SWIDE = 32;     // widest state row of the WIDE first-layer passes (Blk's WIDE)
+// LDS row stride of a state row: 8 floats up to S = 8 (as the narrow kernels have it), else the next multiple of 4
+__host__ __device__ inline int xld_for(int S) { return S <= SMAX ? SMAX : (S + 3) & ~3; }
 
 // Row stride (bytes) of the byte masks for NT16 N tiles: 4*odd dwords, so that the dword a lane reads in the
 // backward GEMM (row 16mt+c, bytes nc+4g..+3) sits in bank (4*odd*c + g + const) mod 64: conflict-free for all lanes.
@@ -239,7 +242,9 @@ struct HeadExtra {
 // instead of row c, block (g, c / 4) of the instruction accumulates rows 0..3 x columns 4(c/4)..+3 over the k's of lane
 // group g; a butterfly over g after the loop (tail_finish) completes the sum, and lanes g == 0 hold rows 0..3 of column
 // c -- exactly what they hold of a 16x16x4 accumulator, so every epilogue is unchanged (lanes g > 0 = rows 4..15 = 0).
-template <int MT, int NTW, int MSTRIDE, bool LERP = false, bool TADAM = false, bool T4 = false>
+// WIDE: the first-layer passes (trunk, trunk_grad_adam) take a state row of up to SWIDE floats with row stride
+// xld_for(S) and walk it in chunks of SMAX inputs (trunk_wide, trunk_grad_adam_wide); otherwise rows are SMAX floats.
+template <int MT, int NTW, int MSTRIDE, bool LERP = false, bool TADAM = false, bool T4 = false, bool WIDE = false>
 struct Blk {
     static constexpr int MB = MT * 16;
     static constexpr int TROW = 16 * (MT - 1);          // first row of the last batch tile
@@ -321,6 +326,7 @@ struct Blk {
     template <class WP>
     __device__ __forceinline__ void trunk(WP W1, WP b1, const lds_f32* xs) {
         if constexpr (ablate(3)) return;
+        if constexpr (WIDE) { trunk_wide(W1, b1, xs); return; }
         if (S <= 4) trunk_t<4>(W1, b1, xs);      // wave-uniform: Pendulum-sized states need one 16-byte read per row
         else trunk_t<SMAX>(W1, b1, xs);
     }
@@ -382,6 +388,50 @@ struct Blk {
 #pragma unroll
                 for (int e = 0; e < 4; e++) o[e] = (live4[e] && b < B) ? fmaxf(acc[e] + bias[e], 0.0f) : 0.0f;
                 *reinterpret_cast<lds_f32x4*>(&L.hbuf[b * LDH + 4 * q]) = o;
+            }
+        }
+    }
+    // WIDE: the quad-column form of trunk_t over the state in chunks of SMAX inputs.  One chunk's weights are in
+    // registers at a time; between chunks the running sums rest in hbuf, in the very slot their activation ends up in
+    // (one lane owns a (row, quad) for every chunk: no barrier, and an fp32 round trip through LDS is exact), so an
+    // element is still the i-ascending chain of the narrow form.  State rows: stride xld_for(S), zero beyond S.
+    template <class WP>
+    __device__ __forceinline__ void trunk_wide(WP W1, WP b1, const lds_f32* xs) {
+        const int XLD = xld_for(S);
+        for (int q = lane; 4 * q < LDH; q += 64) {
+            f32x4 bias;
+#pragma unroll
+            for (int e = 0; e < 4; e++) bias[e] = 4 * q + e < H1 ? b1[4 * q + e] : 0.0f;
+            const bool live4[4] = {4 * q < H1, 4 * q + 1 < H1, 4 * q + 2 < H1, 4 * q + 3 < H1};
+            for (int i0 = 0; i0 < S; i0 += SMAX) {
+                f32x4 w[SMAX];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int k = 4 * q + e;
+#pragma unroll
+                    for (int i = 0; i < SMAX; i++) w[i][e] = (k < H1 && i0 + i < S) ? W1[(i0 + i) * H1 + k] : 0.0f;
+                }
+                const bool first = i0 == 0, last = i0 + SMAX >= S;
+                const bool two = i0 + 4 < XLD;           // the chunk's second four inputs lie inside the row
+#pragma unroll 2
+                for (int b = wave; b < MB; b += kWaves) {
+                    lds_f32x4* hp = reinterpret_cast<lds_f32x4*>(&L.hbuf[b * LDH + 4 * q]);
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                    if (!first) acc = *hp;
+                    const f32x4 x0 = *reinterpret_cast<const lds_f32x4*>(&xs[b * XLD + i0]);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) acc += x0[i] * w[i];
+                    if (two) {
+                        const f32x4 x1 = *reinterpret_cast<const lds_f32x4*>(&xs[b * XLD + i0 + 4]);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) acc += x1[i] * w[4 + i];
+                    }
+                    if (last) {
+#pragma unroll
+                        for (int e = 0; e < 4; e++) acc[e] = (live4[e] && b < B) ? fmaxf(acc[e] + bias[e], 0.0f) : 0.0f;
+                    }
+                    *hp = acc;
+                }
             }
         }
     }
@@ -1284,6 +1334,7 @@ struct Blk {
                                                     float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
                                                     const lds_f32* xs, EXTRA extra = EXTRA{}, lds_f32* stage = nullptr) {
         if constexpr (ablate(7)) return;
+        if constexpr (WIDE) { trunk_grad_adam_wide<EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs); return; }
         if (S <= 4) trunk_grad_adam_t<4, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra, stage);     // wave-uniform
         else trunk_grad_adam_t<SMAX, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra, stage);
     }
@@ -1355,6 +1406,75 @@ struct Blk {
                         if (stage) stage[is_bias ? S * H1 + k : s * H1 + k] = nv;
                         if (tap) tap[p] = gr;
                         if (tt) tt[p] = polyak(o, nv, tau);
+                    }
+                }
+            }
+        }
+    }
+
+    // WIDE: the same with the state walked in chunks of SMAX inputs, chunk outermost: dh1 of the wave's elements is
+    // regenerated per chunk from the live accumulators and the hbuf signs (a select each), so that only one chunk's SMAX
+    // column sums are in registers beside the accumulators; every sum over the batch keeps the narrow form's order.  The
+    // bias goes with the last chunk.
+    template <class EXTRA, bool GONLY>
+    __device__ __forceinline__ void trunk_grad_adam_wide(const f32x4 (&acc)[MT][NTW], float* th, float* m, float* v,
+                                                         float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
+                                                         const lds_f32* xs) {
+        static_assert(std::is_same<EXTRA, NoExtra>::value, "the wide first-layer gradient has no head term");
+        const int NT = (H1 + 15) >> 4;
+        const int XLD = xld_for(S);
+#pragma unroll
+        for (int i = 0; i < NTW; i++) {
+            const int t = tile_of(i);
+            if (t >= NT) continue;
+            const int k = 16 * t + c;
+            for (int s0 = 0; s0 < S; s0 += SMAX) {
+                const bool two = s0 + 4 < XLD;
+                float gb = 0.0f;
+                float gw[SMAX];
+#pragma unroll
+                for (int s = 0; s < SMAX; s++) gw[s] = 0.0f;
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int b = 16 * mt + 4 * g + r;
+                        const float hv = L.hbuf[b * LDH + (k < H1 ? k : 0)];
+                        const float d = (k < H1 && hv > 0.0f) ? acc[mt][i][r] : 0.0f;
+                        gb += d;
+                        const f32x4 x0 = *reinterpret_cast<const lds_f32x4*>(&xs[b * XLD + s0]);
+#pragma unroll
+                        for (int s = 0; s < 4; s++) gw[s] += x0[s] * d;
+                        if (two) {
+                            const f32x4 x1 = *reinterpret_cast<const lds_f32x4*>(&xs[b * XLD + s0 + 4]);
+#pragma unroll
+                            for (int s = 0; s < 4; s++) gw[4 + s] += x1[s] * d;
+                        }
+                    }
+                }
+                gb = col4_sum(gb);
+#pragma unroll
+                for (int s = 0; s < SMAX; s++) gw[s] = col4_sum(gw[s]);
+                const int nr = S - s0 < SMAX ? S - s0 : SMAX;          // weight rows of this chunk
+                const int nslot = nr + (s0 + SMAX >= S ? 1 : 0);       // + the bias behind the last chunk's rows
+                if (k < H1) {
+                    for (int s = g; s < nslot; s += 4) {
+                        const bool is_bias = s == nr;
+                        float gr = gb;
+#pragma unroll
+                        for (int q = 0; q < SMAX; q++)
+                            if (q == s && !is_bias) gr = gw[q];
+                        const int p = is_bias ? ob1 + k : oW1 + (s0 + s) * H1 + k;
+                        if constexpr (GONLY) {
+                            tap[p] = gr;
+                        } else {
+                            float mm = m[p], vv = v[p];
+                            const float o = tt ? tt[p] : 0.0f;
+                            const float nv = astep_small(th[p], gr, mm, vv, alpha);
+                            m[p] = mm; v[p] = vv; th[p] = nv;
+                            if (tap) tap[p] = gr;
+                            if (tt) tt[p] = polyak(o, nv, tau);
+                        }
                     }
                 }
             }
@@ -1707,7 +1827,7 @@ struct Blk {
 #pragma unroll
                 for (int j = 0; j < NE; j++) {
                     const float gr = col4_sum(ge[j]);
-                    if (g == j && nok) {
+                    if (g == (NE > 4 ? (j & 3) : j) && nok) {      // (more than four extra rows: lane group j mod 4)
                         const size_t p = rlc_blk_index(((H1 + 15) & ~15) + j, n, N);   // first extra block row + j
                         if constexpr (GONLY) { tapp[p] = gr; continue; }
                         float mm = mp[p], vv = vp[p];

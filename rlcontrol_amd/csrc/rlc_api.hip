@@ -775,7 +775,6 @@ static int launch_update(rlc_handle* h, int first, int n, int n_updates, int sou
         return rlc_h_split_after_launch(h);
     }
     if (v == 2) {
-        RLC_REQUIRE(rlc_mfma_supported(h->dv.d), "MFMA kernel does not support these dimensions");
         return rlc_launch_ddpg_update_mfma(h->dv, first, n, n_updates, source, idx_dev, h->grad_taps, h->st);
     }
     return rlc_launch_ddpg_update_generic(h->dv, first, n, n_updates, source, idx_dev, h->grad_taps, h->st);
@@ -799,8 +798,10 @@ int rlc_ddpg_update_batch(rlc_handle* h, int32_t agent, int32_t batch, const dou
 }
 
 int rlc_ddpg_set_kernel(rlc_handle* h, int32_t variant) {
+    // 2 also takes the wide shapes (state_dim <= 32, action_dim in {1,2,3,4,6}), which 0 leaves on the any-shape kernel
+    const char* why = h && h->algo == RLC_ALGO_DDPG && variant == 2 ? rlc_mfma_refusal(h->dv.d) : nullptr;
     return rlc_h_set_kernel(h, RLC_ALGO_DDPG, variant,
-                            h && !rlc_mfma_supported(h->dv.d) ? "MFMA kernel does not support these dimensions" : "");
+                            why ? std::string("MFMA kernel does not support these dimensions: ") + why : std::string());
 }
 
 int rlc_ddpg_get_kernel(const rlc_handle* h, int32_t* variant_in_use) {
@@ -811,6 +812,7 @@ int rlc_ddpg_set_split(rlc_handle* h, int32_t n_workgroups) {
     if (int rc = rlc_h_split_check(h, RLC_ALGO_DDPG, n_workgroups)) return rc;
     if (n_workgroups == 1) return 0;
     RLC_REQUIRE(rlc_h_variant(h) == 2, "the split update is a variant of the MFMA kernel (these dimensions run the generic one)");
+    RLC_REQUIRE(rlc_mfma_supported(h->dv.d), "latency mode runs state_dim <= 8, action_dim <= 2 (the split kernel has no wide form)");
     RLC_REQUIRE(!h->dv.d.sep, "latency mode is built for the hydra network (network: separate runs the one-workgroup kernels)");
     RLC_REQUIRE(rlc_split_mt(h->dv.d.B, n_workgroups) > 0, "batch_size %d does not fit %d workgroups of at most 64 rows",
                 h->dv.d.B, n_workgroups);

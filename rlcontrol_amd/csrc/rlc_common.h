@@ -268,7 +268,11 @@ enum RlcBatchSource { RLC_SRC_REPLAY_DEVICE_SAMPLER = 0, RLC_SRC_REPLAY_HOST_IND
 int rlc_launch_ddpg_update_generic(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source,
                                    const long long* idx_dev, int grad_taps, hipStream_t st,
                                    const RlcRollout* rollout = nullptr, int q8_first = 0);
-// MFMA-tiled fused update (dims must satisfy rlc_mfma_supported)
+// MFMA-tiled fused update.  rlc_mfma_refusal: null, or the limit these dimensions exceed (layer norm; widths multiples of
+// 4 in [16, 256]; state_dim <= 32; action_dim in {1,2,3,4,6}; batch_size <= 128; LDS bytes needed against 163,840).
+// rlc_mfma_supported: the shapes it is the default for (state_dim <= 8, action_dim <= 2) -- above them it runs on
+// request only (rlc_ddpg_set_kernel), in its wide form.
+const char* rlc_mfma_refusal(const RlcDims& d);
 bool rlc_mfma_supported(const RlcDims& d);
 // batch-split latency mode (ddpg_split.hip): C workgroups per agent; part [n_agents][C][Ppad] zero-initialised, bar
 // [n_agents], err [1]; rlc_split_mt: M tiles per workgroup for (batch, C), 0 if unsupported
