@@ -227,8 +227,12 @@ int rlc_sac_update_batch(rlc_sac* h, int32_t agent, int32_t batch, const double*
 int rlc_sac_last_tap(rlc_sac* h, int32_t agent, int32_t which, float* dst, int64_t n);
 int rlc_sac_enable_grad_taps(rlc_sac* h, int32_t on);
 /* kernel selection (no reference counterpart: one tf.Graph there): 0 auto, 1 generic fp32 VALU kernel (any shape),
- * 2 MFMA kernel (S <= 8, A <= 2, layer widths multiples of 4 in [16,256], LDS permitting).  Switching re-packs the
- * weights between the row-major and the tile-blocked device layout; results differ only in summation order. */
+ * 2 MFMA kernel.  0 chooses the MFMA kernel at state_dim <= 8, action_dim <= 2 (no layer norm, layer widths multiples
+ * of 4 in [16, 256], batch_size <= 128, LDS <= 160 KiB) and the generic kernel everywhere else.  2 also takes the wide
+ * shapes -- state_dim <= 32, action_dim in {1, 2, 3, 4, 6}, the other limits as above -- which run on request only; a
+ * refusal reads "MFMA SAC kernel does not support these dimensions: <the limit exceeded>" (the LDS limit with the bytes
+ * needed and allowed).  Switching re-packs the weights and the optimizer state between the row-major and the
+ * tile-blocked device layout; results differ only in summation order. */
 int rlc_sac_set_kernel(rlc_sac* h, int32_t variant);
 int rlc_sac_get_kernel(const rlc_sac* h, int32_t* variant_in_use);
 

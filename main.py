@@ -87,7 +87,7 @@ _SHARED_KEYS = {
     "DDPG": ("shared_l1_dim", "actor_l2_dim", "critic_l2_dim", "batch_size", "buffer_size", "tau", "gamma",
              "warmup_steps", "norm_type", "network", "exploration_policy", "ou_theta", "ou_mu", "ou_sigma"),
     "SoftActorCritic": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size",
-                        "tau", "gamma", "warmup_steps", "norm_type", "exploration_policy", "sample_for_eval"),
+                        "tau", "gamma", "warmup_steps", "norm_type", "exploration_policy", "sample_for_eval", "hip_kernel"),
     "NAF": ("l1_dim", "l2_dim", "batch_size", "buffer_size", "tau", "gamma", "warmup_steps", "norm_type",
             "exploration_policy"),
     "ReverseKL": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size", "tau",
@@ -179,6 +179,13 @@ def _make_population(agent_name, members, arg_params):
     for i, m in enumerate(members):
         pop.set_params(i, init_params(c0.state_dim, c0.action_dim, c0.actor_l1_dim, c0.actor_l2_dim, c0.critic_l1_dim,
                                       c0.critic_l2_dim, m[3].random_seed, c0.norm_type), init_target=True)
+    # optional json key "hip_kernel" as in agents/SoftActorCritic.py (the device environments' shapes are narrow: "mfma"
+    # and "auto" choose the same kernel there)
+    kernel = getattr(c0, "hip_kernel", "auto")
+    if kernel not in SACPopulation.KERNEL:
+        raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(SACPopulation.KERNEL)))
+    if kernel != "auto":
+        pop.set_kernel(kernel)
     return pop
 
 

@@ -35,7 +35,6 @@ int rlc_h_sac_launch_update(rlc_handle* h, int first, int n, int n_updates, int 
         return rlc_launch_kl_update(h->sac, first, n, n_updates, source, idx_dev, eps_dev, h->grad_taps, h->st, rollout);
     }
     if (rlc_h_variant(h) == 2) {
-        RLC_REQUIRE(rlc_sac_mfma_supported(h->sac.d), "MFMA SAC kernel does not support these dimensions");
         return rlc_launch_sac_update_mfma(h->sac, first, n, n_updates, source, idx_dev, eps_dev, h->grad_taps, h->st, rollout);
     }
     return rlc_launch_sac_update(h->sac, first, n, n_updates, source, idx_dev, eps_dev, h->grad_taps, h->st, rollout);
@@ -152,8 +151,10 @@ int rlc_sac_update_batch(rlc_handle* h, int32_t agent, int32_t batch, const doub
     return rlc_sacfam_update_batch(RLC_ALGO_SAC, h, agent, batch, states, actions, next_states, rewards, gammas, eps);
 }
 int rlc_sac_set_kernel(rlc_handle* h, int32_t variant) {
+    // 2 also takes the wide shapes (state_dim <= 32, action_dim in {1,2,3,4,6}), which 0 leaves on the any-shape kernel
+    const char* why = h && h->algo == RLC_ALGO_SAC && variant == 2 ? rlc_sac_mfma_refusal(h->sac.d) : nullptr;
     return rlc_h_set_kernel(h, RLC_ALGO_SAC, variant,
-                            h && !rlc_sac_mfma_supported(h->sac.d) ? "MFMA SAC kernel does not support these dimensions" : "");
+                            why ? std::string("MFMA SAC kernel does not support these dimensions: ") + why : std::string());
 }
 int rlc_sac_get_kernel(const rlc_handle* h, int32_t* variant_in_use) { return rlc_h_get_kernel(h, RLC_ALGO_SAC, variant_in_use); }
 int rlc_sac_enable_grad_taps(rlc_handle* h, int32_t on) { return rlc_h_enable_grad_taps(h, RLC_ALGO_SAC, on); }

@@ -92,7 +92,13 @@ struct RlcSacRollout;   // sac_rollout_device.h: {RlcSacDev, RlcEnvDev} in devic
 int rlc_launch_sac_update(const RlcSacDev& dv, int first_agent, int n_agents, int n_updates, int source,
                           const long long* idx_dev, const float* eps_dev, int grad_taps, hipStream_t st,
                           const RlcSacRollout* rollout = nullptr);
-// MFMA-tiled fused update (dims must satisfy rlc_sac_mfma_supported; tile-blocked layout)
+// MFMA-tiled fused update (tile-blocked layout).  rlc_sac_mfma_refusal: null, or the limit these dimensions exceed (layer
+// norm; the KL agents' Q network; widths multiples of 4 in [16, 256]; state_dim <= 32; action_dim in {1,2,3,4,6};
+// batch_size <= 128; LDS bytes needed against 163,840).  rlc_sac_mfma_supported: the shapes the kernel is the default for
+// (state_dim <= 8, action_dim <= 2) -- above them (rlc_sac_mfma_wide) it runs on request only (rlc_sac_set_kernel), in
+// its wide form.
+inline bool rlc_sac_mfma_wide(const RlcSacDims& d) { return d.S > 8 || d.A > 2; }
+const char* rlc_sac_mfma_refusal(const RlcSacDims& d);
 bool rlc_sac_mfma_supported(const RlcSacDims& d);
 int rlc_launch_sac_update_mfma(const RlcSacDev& dv, int first_agent, int n_agents, int n_updates, int source,
                                const long long* idx_dev, const float* eps_dev, int grad_taps, hipStream_t st,

@@ -22,7 +22,9 @@
 //   correction is log(clip(1 - pi^2, 0, 1) + 1e-6) with the clip passing gradients;
 //   r and gamma enter fp32 placeholders (sac_network.py:51-52): the replay's float64 values are cast at gather time.
 //
-// Supported shapes: S <= 8, A in {1,2}, layer widths multiples of 4 in [16, 128*NTW], B <= 128, LDS <= 160 KiB.
+// Supported shapes: S <= 8, A in {1,2}, layer widths multiples of 4 in [16, 128*NTW], B <= 128, LDS <= 160 KiB; in the
+// WIDE form (opt-in through rlc_sac_set_kernel, see rlc_sac_mfma_wide) S <= 32 and A in {1,2,3,4,6}.  The quirks above
+// need scalars only (state_min[0] / state_max[0] / action_max[0]): the WIDE form adds no per-dimension array.
 #pragma once
 #include "mfma_blocks.h"
 #include "sac_rollout_device.h"
@@ -93,6 +95,44 @@ __host__ __device__ inline size_t ssmem_carve(const RlcSacDims& d, int MT, lds_u
     return off;
 }
 
+// The carve of the WIDE form (rlc_sac_mfma_wide shapes; a function of its own: the narrow carve above stays as it is).
+// State rows lie at stride xld_for(S).  Q(s,pi) | dQ/da partials (`part_p`) share the bytes of the pi head partials
+// (`part_h`): the last read of part_h (mu, log_std -> sample, logp) and the first write of part_p (concat_head_dots) have
+// always had a barrier between them, so the alias costs none.  No scratch of the on-device loop (`pol`) and no staged
+// first layers: the WIDE form runs neither.
+template <int MSTRIDE>
+__host__ __device__ inline size_t ssmem_carve_wide(const RlcSacDims& d, int MT, lds_u8* base, SSmem* out) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        lds_u8* p = base + off;
+        off += (bytes + 15) & ~(size_t)15;
+        return p;
+    };
+    const int MB = MT * 16, A = d.A, LDH = sac_mfma_ldh(d), XL = xld_for(d.S);
+    SSmem L;
+    L.hbuf = (lds_f32*)take(sizeof(float) * (MB * LDH + 16));
+    L.idx = (lds_i64*)take(sizeof(long long) * RLC_MAX_BATCH);
+    L.mask = take((size_t)MB * MSTRIDE);
+    L.part_h = (lds_f32*)take(sizeof(float) * kWaves * MB * 2 * A);      // 2A >= 1 + A
+    L.part_p = L.part_h;
+    L.part_q = (lds_f32*)take(sizeof(float) * kWaves * MB);
+    L.wvec = (lds_f32*)take(sizeof(float) * 2 * A * 256);
+    lds_f32** ps[] = {&L.x, &L.xc, &L.x2c};
+    for (auto p : ps) *p = (lds_f32*)take(sizeof(float) * MB * XL);
+    lds_f32** pa[] = {&L.a, &L.api, &L.eps, &L.pit, &L.sd, &L.t};
+    for (auto p : pa) *p = (lds_f32*)take(sizeof(float) * MB * A);
+    L.dml = (lds_f32*)take(sizeof(float) * MB * 2 * A);
+    lds_f32** pb[] = {&L.r, &L.g, &L.vt, &L.q, &L.qpi, &L.v, &L.logp, &L.dout, &L.dvs};
+    for (auto p : pb) *p = (lds_f32*)take(sizeof(float) * MB);
+    L.red = (lds_f32*)take(sizeof(float) * 16);
+    L.pool = (lds_i32*)take(sizeof(int) * 3 * RLC_MAX_BATCH);
+    L.dups = (lds_i32*)take(sizeof(int) * 4);
+    L.pol = nullptr;
+    L.w1vt = L.w1q = L.w1p = L.w1v = nullptr;
+    if (out) *out = L;
+    return off;
+}
+
 // block-wide sum of v over threads (fixed order: deterministic); result broadcast to all threads
 __device__ inline float sac_blk_sum(float v, lds_f32* red) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -117,7 +157,9 @@ __device__ inline void sac_blk_sum2(float a, float b, lds_f32* red, float& sa, f
 }
 
 // T4: the minibatch ends within the first four rows of its last tile (mfma_blocks.h, Blk's T4; the launcher checks it)
-template <int MT, int NTW, int AD, bool T4>
+// WIDE: the form for rlc_sac_mfma_wide shapes (Blk's WIDE first-layer passes -- all seven of an update and the three
+// first-layer gradients --, the carve above); the narrow instantiations hold none of its code
+template <int MT, int NTW, int AD, bool T4, bool WIDE = false>
 __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev dv, int first_agent, int n_updates,
                                                                        int source, const long long* host_idx,
                                                                        const float* eps_in, int grad_taps,
@@ -125,14 +167,21 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int MSTRIDE = mask_stride(8 * NTW);
     constexpr int NS = 2 * AD;
-    using U = Blk<MT, NTW, MSTRIDE, true, false, T4>;
+    using U = Blk<MT, NTW, MSTRIDE, true, false, T4, WIDE>;
+    static_assert(WIDE || AD <= 2, "more than two action columns: the WIDE form");
+    static_assert(!(WIDE && T4), "the WIDE form has no tail-of-four units");
+#ifdef RLC_W1_STAGE
+    static_assert(!WIDE, "the staged first layers are sized for SMAX state rows");
+#endif
     constexpr int MB = U::MB;
     const RlcSacDims d = dv.d;
     U u;
     u.init_geometry();
     u.S = d.S; u.H1 = d.L1A; u.B = d.B; u.LDH = sac_mfma_ldh(d);
+    const int XL = WIDE ? xld_for(d.S) : SMAX;       // floats between state rows in LDS
     SSmem L;
-    ssmem_carve<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
+    if constexpr (WIDE) ssmem_carve_wide<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
+    else ssmem_carve<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
     u.L.hbuf = L.hbuf; u.L.mask = L.mask;
     const int tid = u.tid, S = d.S, L1A = d.L1A, L2A = d.L2A, L1C = d.L1C, L2C = d.L2C, B = d.B;
     const int agent = first_agent + blockIdx.x;
@@ -155,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
     // zero the padded tails of the per-sample vectors once (rows >= B never change afterwards)
     for (int i = tid; i < MB * AD; i += kThreads) { L.a[i] = 0.f; L.api[i] = 0.f; L.eps[i] = 0.f; L.pit[i] = 0.f; L.sd[i] = 0.f; L.t[i] = 0.f; }
     for (int i = tid; i < MB * NS; i += kThreads) L.dml[i] = 0.f;
-    for (int i = tid; i < MB * SMAX; i += kThreads) { L.x[i] = 0.f; L.xc[i] = 0.f; L.x2c[i] = 0.f; }
+    for (int i = tid; i < MB * XL; i += kThreads) { L.x[i] = 0.f; L.xc[i] = 0.f; L.x2c[i] = 0.f; }
     for (int i = tid; i < MB; i += kThreads) {
         L.r[i] = 0.f; L.g[i] = 0.f; L.vt[i] = 0.f; L.q[i] = 0.f; L.qpi[i] = 0.f; L.v[i] = 0.f; L.logp[i] = 0.f;
         L.dout[i] = 0.f; L.dvs[i] = 0.f;
@@ -186,8 +235,11 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
         stamp_i = 0;
         if (tid == 0) t_prev = clock64();
 #endif
-        asm volatile("" : "+v"(u.c), "+v"(u.g), "+s"(u.wave));     // see ddpg_mfma_kernel.h
-        if (rollout) {
+        // (see ddpg_mfma_kernel.h; WIDE leaves the wave number alone: at twelve head columns hipcc 7.2 cannot keep it in
+        // the scalar register the constraint asks for and stops with "illegal VGPR to SGPR copy")
+        if constexpr (WIDE) asm volatile("" : "+v"(u.c), "+v"(u.g));
+        else asm volatile("" : "+v"(u.c), "+v"(u.g), "+s"(u.wave));
+        if (!WIDE && rollout) {
             // on-device experiment loop: one environment step first; update when learn() would run
             if (!rlc_sac_train_step_device(rollout, agent, (float*)L.pol)) continue;
         }
@@ -226,9 +278,9 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
                 L.r[b] = (float)ld_gather(&dv.rep.rr[slot]); L.g[b] = (float)ld_gather(&dv.rep.rg[slot]);
             }
             for (int i = 0; i < S; i++) {
-                L.x[b * SMAX + i] = ld_gather(&ps[i]);
-                L.xc[b * SMAX + i] = rlc_clip_scalar(ld_gather(&ps[i]), dv.clip_state, dv.smin0, dv.smax0);
-                L.x2c[b * SMAX + i] = rlc_clip_scalar(ld_gather(&ps2[i]), dv.clip_state, dv.smin0, dv.smax0);
+                L.x[b * XL + i] = ld_gather(&ps[i]);
+                L.xc[b * XL + i] = rlc_clip_scalar(ld_gather(&ps[i]), dv.clip_state, dv.smin0, dv.smax0);
+                L.x2c[b * XL + i] = rlc_clip_scalar(ld_gather(&ps2[i]), dv.clip_state, dv.smin0, dv.smax0);
             }
 #pragma unroll
             for (int j = 0; j < AD; j++) {
@@ -456,7 +508,15 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
                     }
                 }
             }
-            if (u.wave < NS) {            // bm[j] / bs[j]: sum_b of the seeds, wave j
+            if constexpr (WIDE) {         // up to 12 head columns: wave j mod 8
+                for (int j = u.wave; j < NS; j += kWaves) {
+                    float gr = 0.0f;
+                    for (int b = u.lane; b < MB; b += 64) gr += L.dml[b * NS + j];
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) gr += __shfl_xor(gr, off, 64);
+                    if (u.lane == 0) U::adam_scalar(th, mm, vv, tt, tapg, j < AD ? d.pbm + j : d.pbs + (j - AD), gr, alpha_p, tau);
+                }
+            } else if (u.wave < NS) {            // bm[j] / bs[j]: sum_b of the seeds, wave j
                 const int j = u.wave;
                 float gr = 0.0f;
                 for (int b = u.lane; b < MB; b += 64) gr += L.dml[b * NS + j];
@@ -600,14 +660,17 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
 #undef STAMP
 }
 
-template <int MT, int NTW, int AD, bool T4>
+template <int MT, int NTW, int AD, bool T4, bool WIDE = false>
 int sac_launch_t(const RlcSacDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
                  const float* eps_dev, int grad_taps, hipStream_t st, const RlcSacRollout* rollout) {
     constexpr int MSTRIDE = mask_stride(8 * NTW);
-    const size_t lds = ssmem_carve<MSTRIDE>(dv.d, MT, nullptr, nullptr);
+    const size_t lds = WIDE ? ssmem_carve_wide<MSTRIDE>(dv.d, MT, nullptr, nullptr) : ssmem_carve<MSTRIDE>(dv.d, MT, nullptr, nullptr);
     RLC_REQUIRE(lds <= 160 * 1024, "MFMA SAC kernel needs %zu B of LDS (> 160 KiB)", lds);
     RLC_REQUIRE(!T4 || rlc_tail4(dv.d.B, MT), "tail-of-four kernel launched for batch %d", dv.d.B);
-    auto kern = rlc_sac_update_mfma_kernel<MT, NTW, AD, T4>;
+    RLC_REQUIRE(WIDE == rlc_sac_mfma_wide(dv.d), "state_dim %d / action_dim %d on the %s form of the MFMA SAC kernel", dv.d.S,
+                dv.d.A, WIDE ? "wide" : "narrow");
+    RLC_REQUIRE(!(WIDE && rollout), "the on-device experiment loop runs the narrow MFMA kernel (state_dim <= 8, action_dim <= 2)");
+    auto kern = rlc_sac_update_mfma_kernel<MT, NTW, AD, T4, WIDE>;
     static bool attr_set = false;
     if (!attr_set) {
         RLC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -52,6 +52,9 @@ def init_params(S, A, L1A, L2A, L1C, L2C, seed, norm_type="input_norm"):
 
 
 class SACPopulation(SampledPolicyPopulation):
+    """set_kernel("auto") (the default of a new population) runs the MFMA kernel at state_dim <= 8, action_dim <= 2 and
+    the any-shape kernel elsewhere; set_kernel("mfma") also takes state_dim <= 32 with action_dim in {1, 2, 3, 4, 6} (the
+    wide form, on request only) and raises RlcError naming the limit for anything else."""
     PREFIX = "rlc_sac"
     TAP = {"q": 0, "v": 1, "logp": 2, "q_pi": 3, "loss": 4, "grads": 5}
 
