@@ -87,6 +87,22 @@ GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic
 USAGE_JSON = os.path.join(_HERE, "kernel_resource_usage.json")
 
 
+def extract_code_object(obj, out):
+    """Write the gfx950 code object bundled in the compiled unit `obj` to `out`; False for a host-only unit (no device
+    code in it).  What audit_object reads, and what scripts/compare_code_objects.py hashes."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        fb = os.path.join(tmp, "x.hipfb")
+        # (an explicit output file: with one positional argument llvm-objcopy rewrites `obj` in place, and the library
+        # then looks older than its objects)
+        if subprocess.call([os.path.join(_LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, obj,
+                            os.path.join(tmp, "x.o")], stderr=subprocess.DEVNULL) != 0:
+            return False
+        subprocess.check_call([os.path.join(_LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fb,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + out])
+    return True
+
+
 def audit_object(obj):
     """Per-kernel register / spill report of one compiled unit, read back from the gfx950 code object inside `obj`:
     vgpr_count, sgpr_spill_count, vgpr_spill_count, scratch bytes (the code object's metadata = what
@@ -100,14 +116,9 @@ def audit_object(obj):
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        fb, co = os.path.join(tmp, "x.hipfb"), os.path.join(tmp, "x.co")
-        # (an explicit output file: with one positional argument llvm-objcopy rewrites `obj` in place, and the library
-        # then looks older than its objects)
-        if subprocess.call([os.path.join(_LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, obj,
-                            os.path.join(tmp, "x.o")], stderr=subprocess.DEVNULL) != 0:
+        co = os.path.join(tmp, "x.co")
+        if not extract_code_object(obj, co):
             return {}                     # a host-only unit: no device code in it
-        subprocess.check_call([os.path.join(_LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fb,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
         notes = subprocess.check_output([os.path.join(_LLVM, "llvm-readelf"), "--notes", co], text=True)
         dis = subprocess.check_output([os.path.join(_LLVM, "llvm-objdump"), "-d", "--symbolize-operands",
                                        "--no-show-raw-insn", co], text=True)

@@ -31,7 +31,8 @@ struct Smem {
     lds_i32* pool;
     lds_i32* dups;
     lds_f32x4* xbuf;    // hand-off of the split 13th tile (mfma_blocks.h)
-    lds_f32 *w1t, *w1o; // first layer staged in LDS ([S][H1] weights, [H1] biases): target / online (mfma_blocks.h stage_*)
+    lds_f32 *w1t, *w1o; // always null (the retired staged-first-layer experiment): part of the struct's image
+                        // in scratch -- taking them out moves the kernel's scratch offsets, so a change of its own
 };
 
 // shapes that only the WIDE form of the kernel takes: a state row above SMAX floats or more than two action columns
@@ -85,12 +86,7 @@ __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* b
     } else {
         L.xbuf = (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4));
     }
-#ifdef RLC_W1_STAGE
-    L.w1t = (lds_f32*)take(sizeof(float) * (d.S + 1) * d.H1);
-    L.w1o = (lds_f32*)take(sizeof(float) * (d.S + 1) * d.H1);
-#else
     L.w1t = L.w1o = nullptr;
-#endif
     if (out) *out = L;
     return off;
 }
@@ -109,9 +105,6 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
     using U = Blk<MT, NTW, MSTRIDE, false, false, T4, WIDE>;
     static_assert(WIDE || AD <= 2, "more than two action columns: the WIDE form");
     static_assert(!(WIDE && T4), "the WIDE form has no tail-of-four units");
-#ifdef RLC_W1_STAGE
-    static_assert(!WIDE, "the staged first layer is sized for SMAX state rows");
-#endif
     constexpr int MB = U::MB;
     const RlcDims d = dv.d;
     U u;
@@ -157,10 +150,6 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
     if (tid < 16) L.hbuf[MB * u.LDH + tid] = 0.0f;
     __syncthreads();
 
-    stagger_start();
-#ifdef RLC_PRIO_YOUNG
-    if (u.wave >= 4) __builtin_amdgcn_s_setprio(1);     // the second-dispatched half loses every issue arbitration otherwise
-#endif
     f32x4 acc[MT][NTW];
 #ifdef RLC_STAMPS
     // diagnostic build only: phase boundaries in shader cycles, written where the critic gradient tap lives
@@ -191,12 +180,6 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             // (agents/base_agent.py:65-70).  hbuf is free here (the trunk overwrites it below).
             if (!rlc_train_step_device(rollout, agent, (float*)L.hbuf, upd == 0 ? q8_first : 0)) continue;
         }
-#ifdef RLC_W1_STAGE
-        // both first layers go in flight now and land in LDS behind the minibatch gather
-        float stg_t[U::kStage], stg_o[U::kStage];
-        u.stage_load(stg_t, tt + d.oW1, tt + d.ob1);
-        u.stage_load(stg_o, th + d.oW1, th + d.ob1);
-#endif
         // ================= sample + gather (utils/replaybuffer.py:32-37) =================
         if (!(ablate(4) && upd > 0)) {
         u.sub_begin();
@@ -221,47 +204,39 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             } else {
                 const size_t slot = (size_t)agent * dv.rep.cap + ring_slot(ring, dv.rep.cap, L.idx[b]);
                 ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot * AD; ps2 = dv.rep.rs2 + slot * S;
-                L.r[b] = ld_gather(&dv.rep.rr[slot]); L.g[b] = ld_gather(&dv.rep.rg[slot]);
+                L.r[b] = dv.rep.rr[slot]; L.g[b] = dv.rep.rg[slot];
             }
             for (int i = 0; i < S; i++) {
-                L.x[b * XL + i] = clip_state_val(ld_gather(&ps[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
-                L.x2[b * XL + i] = clip_state_val(ld_gather(&ps2[i]), dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x[b * XL + i] = clip_state_val(ps[i], dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x2[b * XL + i] = clip_state_val(ps2[i], dv.clip_state, dv.smin[i], dv.smax[i]);
             }
 #pragma unroll
-            for (int j = 0; j < AD; j++) L.a[b * AD + j] = ld_gather(&pa[j]);
+            for (int j = 0; j < AD; j++) L.a[b * AD + j] = pa[j];
         }
         u.sub_stamp(27);
         }
-#ifdef RLC_W1_STAGE
-        u.stage_store(stg_t, L.w1t);
-        u.stage_store(stg_o, L.w1o);
-#endif
-        lds_barrier();
+        __syncthreads();
         STAMP();
 
         // ================= steps 1-2: target networks on s' (DDPG.py:77) =================
-#ifdef RLC_W1_STAGE
-        u.trunk((const lds_f32*)L.w1t, (const lds_f32*)(L.w1t + S * H1), L.x2);
-#else
         u.trunk(tt + d.oW1, tt + d.ob1, L.x2);
-#endif
-        lds_barrier();
+        __syncthreads();
         STAMP();
         // target actor and target critic read the same trunk image and the critic needs the actor's output only in its
         // epilogue (the action rows): one k-loop for both hidden contractions when the two layers have one width
         // (mfma_blocks.h fwd_gemm2; +0.9 % at the BASELINE shape, profiles/r03_variant_timings_s9.txt)
         f32x4 acc2[MT][NTW];
-        if constexpr (fuse_fwd) u.template fwd_gemm2<true>(acc, acc2, tt + d.oWa2, tt + d.oWc2, HA, H1);
-        else u.template fwd_gemm<true>(acc, tt + d.oWa2, HA, H1);
+        if constexpr (fuse_fwd) u.fwd_gemm2(acc, acc2, tt + d.oWa2, tt + d.oWc2, HA, H1);
+        else u.fwd_gemm(acc, tt + d.oWa2, HA, H1);
         u.template bias_relu<0>(acc, tt + d.oba2, HA);
         u.template row_dot<false, AD>(acc, HA, [&](int n, int j) { return tt[d.oWa3 + n * AD + j]; }, L.part);   // z' partials
-        lds_barrier();
+        __syncthreads();
         STAMP();
         for (int i = tid; i < B * AD; i += kThreads) {
             const int b = i / AD, j = i % AD;
             L.aout[i] = tanhf(u.template part_sum<AD>(L.part, b, j) + tt[d.oba3 + j]) * amax[j];
         }
-        lds_barrier();
+        __syncthreads();
         STAMP();
         if constexpr (fuse_fwd) {
 #pragma unroll
@@ -271,13 +246,13 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         } else {
             if (sep) {
                 u.trunk(tt + d.oWc1, tt + d.obc1, L.x2);      // the target critic's own first layer
-                lds_barrier();
+                __syncthreads();
             }
-            u.template fwd_gemm<true>(acc, tt + d.oWc2, HC, H1);
+            u.fwd_gemm(acc, tt + d.oWc2, HC, H1);
         }
         u.template bias_relu<AD>(acc, tt + d.obc2, HC, L.aout, tt + d.oWc2, d.arow0);
         u.template row_dot<false, 1>(acc, HC, [&](int n, int) { return tt[d.oWc3 + n]; }, L.part);      // q' partials
-        lds_barrier();
+        __syncthreads();
         STAMP();
         for (int b = tid; b < B; b += kThreads) {
             const float qt = u.template part_sum<1>(L.part, b, 0) + tt[d.obc3];
@@ -285,22 +260,18 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             L.y[b] = y;
             dv.tap_y[(size_t)agent * RLC_MAX_BATCH + b] = y;
         }
-        lds_barrier();
+        __syncthreads();
         STAMP();
 
         // ================= step 3: critic step =================
-#ifdef RLC_W1_STAGE
-        u.trunk((const lds_f32*)L.w1o, (const lds_f32*)(L.w1o + S * H1), L.x);
-#else
         u.trunk(th + d.oWc1, th + d.obc1, L.x);           // the critic's first layer (= the shared trunk in the hydra network)
-#endif
         for (int n = tid; n < 256; n += kThreads) L.wvec[n] = n < HC ? th[d.oWc3 + n] : 0.0f;
-        lds_barrier();
+        __syncthreads();
         STAMP();
         u.fwd_gemm(acc, th + d.oWc2, HC, H1);
         u.template bias_relu<AD>(acc, th + d.obc2, HC, L.a, th + d.oWc2, d.arow0);
         u.template row_dot<false, 1>(acc, HC, [&](int n, int) { return th[d.oWc3 + n]; }, L.part);      // q partials
-        lds_barrier();
+        __syncthreads();
         STAMP();
         for (int b = tid; b < B; b += kThreads) {
             const float q = u.template part_sum<1>(L.part, b, 0) + th[d.obc3];
@@ -308,7 +279,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             dv.tap_q[(size_t)agent * RLC_MAX_BATCH + b] = q;
             L.dq[b] = 2.0f * (q - L.y[b]) / (float)B;                  // d mean((y-q)^2)/dq
         }
-        lds_barrier();
+        __syncthreads();
         STAMP();
         // wave-local column reductions from the live g2 accumulators: dWc3, dbc2; then the relu masks
         float g_wc3[NTW], g_bc2[NTW];
@@ -335,32 +306,20 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             }
         }
         u.template store_masks<-2, true>(acc, HC);
-        lds_barrier();
+        __syncthreads();
         STAMP();
         // dh1 = (dg2 . Wc2[:H1]^T) * relu'(h1) -> W1/b1 gradients -> critic Adam on the trunk (Q1)
         const float alpha_c = adam_alpha(lr_c, pw[2], pw[3]);
         u.template bwd_gemm<1, -2>(acc, th + d.oWc2, HC, H1, L.dq, L.wvec);
-        lds_barrier();      // every wave has finished reading the pre-step Wc2 rows and W1
+        __syncthreads();      // every wave has finished reading the pre-step Wc2 rows and W1
         STAMP();
-        // the first weight-gradient item's W / m / v / W' go in flight before the first-layer gradient, not after it
-        typename U::WgPre2 pre;
-#ifdef RLC_EARLY_PREFETCH
-        constexpr int NPRE = 1;
-        u.template wgrad_prefetch<false, 1>(pre, HC, th + d.oWc2, m_c + d.oWc2, v_c + d.oWc2, tt + d.oWc2);
-#else
-        constexpr int NPRE = 0;
-#endif
-#ifdef RLC_W1_STAGE
-        u.trunk_grad_adam(acc, th, m_c, v_c, alpha_c, d.oW1, d.ob1, tap_gc, nullptr, 0.0f, L.x, NoExtra{}, L.w1o);   // step 4 reads the stepped trunk
-#else
         // hydra: the trunk's target copy follows in the actor step; separate networks: the critic's first layer is
         // Polyak-averaged here, by the only optimizer that owns it
         u.trunk_grad_adam(acc, th, m_c, v_c, alpha_c, d.oWc1, d.obc1, tap_gc, sep ? tt : nullptr, tau, L.x);
-#endif
         STAMP();
         // dWc2 = [h1|a]^T . dg2 with Adam + Polyak in the epilogue
-        u.template wgrad_adam_pre<1, AD, -1, false, false, NPRE>(L.dq, L.a, HC, th + d.oWc2, m_c + d.oWc2, v_c + d.oWc2, alpha_c,
-                     tap_gc ? tap_gc + d.oWc2 : nullptr, tt + d.oWc2, tau, L.wvec, pre);
+        u.template wgrad_adam<1, AD, -1>(L.dq, L.a, HC, th + d.oWc2, m_c + d.oWc2, v_c + d.oWc2, alpha_c,
+                     tap_gc ? tap_gc + d.oWc2 : nullptr, tt + d.oWc2, tau, L.wvec);
         // small critic tensors: Wc3, bc2 (column owners), bc3 (one thread)
         u.sub_begin();
         {
@@ -403,11 +362,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         if (tid == 0) { pw[2] *= 0.9f; pw[3] *= 0.999f; }
 
         // ================= step 4: actor forward with the updated trunk (DDPG.py:90) =================
-#ifdef RLC_W1_STAGE
-        u.trunk((const lds_f32*)L.w1o, (const lds_f32*)(L.w1o + S * H1), L.x);
-#else
         u.trunk(th + d.oW1, th + d.ob1, L.x);
-#endif
         for (int i = tid; i < AD * 256; i += kThreads) {
             const int j = i / 256, n = i % 256;
             L.wvec[i] = n < HA ? th[d.oWa3 + n * AD + j] : 0.0f;       // Wa3 transposed [j][n]
@@ -420,7 +375,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         u.template bias_relu<0>(acc, th + d.oba2, HA);
         u.template row_dot<false, AD>(acc, HA, [&](int n, int j) { return th[d.oWa3 + n * AD + j]; }, L.part);   // z partials
         if constexpr (!WIDE) u.template store_masks<-2, true>(acc, HA);      // (WIDE: the partials lie in the mask bytes)
-        lds_barrier();
+        __syncthreads();
         STAMP();
         for (int i = tid; i < B * AD; i += kThreads) {
             const int b = i / AD, j = i % AD;
@@ -430,7 +385,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             L.aout[i] = ao;
             dv.tap_aout[(size_t)agent * RLC_MAX_BATCH * AD + i] = ao;
         }
-        lds_barrier();
+        __syncthreads();
         STAMP();
         // the h2 accumulators are needed again for dWa3 once dz is known: park them in registers
         f32x4 h2acc[MT][NTW];
@@ -448,7 +403,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         } else {
             if (sep) {
                 u.trunk(th + d.oWc1, th + d.obc1, L.x);       // the stepped critic's first layer at s
-                lds_barrier();
+                __syncthreads();
             }
             u.fwd_gemm(acc, th + d.oWc2, HC, H1);
         }
@@ -456,7 +411,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         // dqda[b][j] = sum_n step(g2[b][n]) * Wc3[n] * Wc2[H1+j][n]
         u.template row_dot<true, AD>(acc, HC, [&](int n, int j) { return th[d.oWc2 + rlc_blk_index(d.arow0 + j, n, HC)] * th[d.oWc3 + n]; },
                                      L.part);
-        lds_barrier();
+        __syncthreads();
         STAMP();
         for (int i = tid; i < B * AD; i += kThreads) {
             const int b = i / AD, j = i % AD;
@@ -465,7 +420,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             const float mu = L.mu[i];
             L.dz[i] = -dqda * (1.0f - mu * mu);                         // grad_ys = -dQ/da on tanh output (Q3)
         }
-        lds_barrier();
+        __syncthreads();
         STAMP();
 
         // ================= step 6: actor step =================
@@ -504,21 +459,18 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             }
         }
         const float alpha_a = adam_alpha(lr_a, pw[0], pw[1]);
-        if constexpr (WIDE) lds_barrier();      // the masks stored above
+        if constexpr (WIDE) __syncthreads();      // the masks stored above
         u.template bwd_gemm<AD, -2>(acc, th + d.oWa2, HA, H1, L.dz, L.wvec);
-        lds_barrier();
+        __syncthreads();
         if (sep) {
             u.trunk(th + d.oW1, th + d.ob1, L.x);             // the actor's image again: its relu mask and the weight-gradient operand
-            lds_barrier();
+            __syncthreads();
         }
         STAMP();
-#ifdef RLC_EARLY_PREFETCH
-        u.template wgrad_prefetch<false, 1>(pre, HA, th + d.oWa2, m_a + d.oWa2, v_a + d.oWa2, tt + d.oWa2);
-#endif
         u.trunk_grad_adam(acc, th, m_a, v_a, alpha_a, d.oW1, d.ob1, tap_ga, tt, tau, L.x);
         STAMP();
-        u.template wgrad_adam_pre<AD, 0, -1, false, false, NPRE>(L.dz, nullptr, HA, th + d.oWa2, m_a + d.oWa2, v_a + d.oWa2, alpha_a,
-                     tap_ga ? tap_ga + d.oWa2 : nullptr, tt + d.oWa2, tau, L.wvec, pre);
+        u.template wgrad_adam<AD, 0, -1>(L.dz, nullptr, HA, th + d.oWa2, m_a + d.oWa2, v_a + d.oWa2, alpha_a,
+                     tap_ga ? tap_ga + d.oWa2 : nullptr, tt + d.oWa2, tau, L.wvec);
         {
             const int NT = (HA + 15) >> 4;
 #pragma unroll
@@ -613,10 +565,8 @@ int launch_tf(const RlcDev& dv, int first_agent, int n_agents, int n_updates, in
 template <int MT, int AD, bool T4, bool WIDE = false>
 int launch_t(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
              int grad_taps, hipStream_t st, const RlcRollout* rollout, int q8_first) {
-#ifndef RLC_DDPG_SEPARATE_FWD
     if (dv.d.HA == dv.d.HC && !dv.d.sep)
         return launch_tf<MT, AD, true, T4, WIDE>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
-#endif
     return launch_tf<MT, AD, false, T4, WIDE>(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, q8_first);
 }
 

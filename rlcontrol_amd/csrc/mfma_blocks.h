@@ -45,7 +45,7 @@ typedef RLC_LDS int lds_i32;
 typedef RLC_LDS double lds_f64;
 typedef RLC_LDS long long lds_i64;
 
-// Timing-only ablations for diagnostic builds (scripts/ab_ablate.sh; results are wrong by construction, the product
+// Timing-only ablations for diagnostic builds (scripts/ab_ablate.py; results are wrong by construction, the product
 // build has RLC_ABLATE == 0): bit 0 no weight-gradient GEMM at all, 1 its k-loops only (no prefetch / Adam epilogue),
 // 2 no action-row loop, 3 no first-layer pass, 4 sample + gather only in the first update of a launch, 5 no backward
 // k-loops, 6 no forward k-loops, 7 no first-layer gradient, 8 no row_dot, 9 no mask stores, 10 no bias_relu,
@@ -54,38 +54,6 @@ typedef RLC_LDS long long lds_i64;
 #define RLC_ABLATE 0
 #endif
 constexpr bool ablate(int bit) { return ((RLC_ABLATE) >> bit) & 1; }
-
-// Experiment switch (diagnostic builds): workgroup i of a launch starts (i mod RLC_STAGGER_WAYS) * RLC_STAGGER_US /
-// RLC_STAGGER_WAYS microseconds late, so that the memory-bound phases of the agents do not coincide chip-wide
-#ifndef RLC_STAGGER_US
-#define RLC_STAGGER_US 0
-#endif
-#ifndef RLC_STAGGER_WAYS
-#define RLC_STAGGER_WAYS 4
-#endif
-__device__ __forceinline__ void stagger_start() {
-    if constexpr (RLC_STAGGER_US > 0) {
-        const long long wait = (long long)(blockIdx.x % RLC_STAGGER_WAYS) * RLC_STAGGER_US * 100 / RLC_STAGGER_WAYS;   // 100 MHz ticks
-        const long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < wait) __builtin_amdgcn_s_sleep(32);
-        __syncthreads();
-    }
-}
-
-// Workgroup barrier for phase boundaries that hand over LDS data only.  __syncthreads() also waits for every outstanding
-// global-memory operation of the wave (s_waitcnt vmcnt(0)): after a phase that stored taps or Adam state, that is a
-// store round trip to HBM on the critical path.  lds_barrier() waits for the wave's LDS / scalar traffic only; global
-// stores keep draining behind it.  Use it only where no wave reads, after the barrier, global data that another wave
-// wrote since the last __syncthreads() (each kernel keeps full barriers at those points).
-// Measured (profiles/r03_variant_timings_s5.txt): no difference on any of the three kernels -- the store round trips are
-// not on the critical path -- so the default stays __syncthreads(); -DRLC_LDS_BARRIERS enables the relaxed form.
-__device__ __forceinline__ void lds_barrier() {
-#ifdef RLC_LDS_BARRIERS
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-    __syncthreads();
-#endif
-}
 
 constexpr int kThreads = 512;
 constexpr int kWaves = 8;     // two waves per SIMD: one can issue MFMA while the other does VALU / waits on loads
@@ -102,58 +70,18 @@ constexpr int mask_stride(int nt16) { return ((nt16 + 1) & 1) ? 16 * (nt16 + 1) 
 // loaded / stored non-temporally (the `nt` bit), so that they do not displace the weight matrices the GEMMs re-read from
 // L2 / the Infinity Cache several times per update.  Measured on one box, 256 agents (profiles/r03_variant_timings_*):
 // m / v: DDPG +3.5 %, SoftActorCritic +8 %, NAF +3.7 %; the target stream on top: DDPG +1.3 %, NAF +3 %, SAC +-0.
-// -DRLC_NO_NT_STATE / -DRLC_NO_NT_TARGET switch them off for A/B runs.
-#ifndef RLC_NO_NT_STATE
-#define RLC_NT_STATE 1
-#endif
-#ifndef RLC_NO_NT_TARGET
-#define RLC_NT_TARGET 1
-#endif
 __device__ __forceinline__ f32x4 ld_stream(const float* p) {
-#ifdef RLC_NT_STATE
     return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-    return *reinterpret_cast<const f32x4*>(p);
-#endif
 }
 __device__ __forceinline__ void st_stream(float* p, f32x4 v) {
-#ifdef RLC_NT_STATE
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 
-// a replay field of the minibatch gather: a random 64-byte sector per field and sample, never re-read
-template <class T>
-__device__ __forceinline__ T ld_gather(const T* p) {
-#ifdef RLC_NT_GATHER
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-// a weight dword of a forward k-loop; STREAM: the matrix is read once per update by this GEMM (a target network's): nt
-template <bool STREAM>
-__device__ __forceinline__ float ld_w(const float* p) {
-#ifdef RLC_NT_TARGET_GEMM
-    if constexpr (STREAM) return __builtin_nontemporal_load(p);
-#endif
-    return *p;
-}
 __device__ __forceinline__ f32x4 ld_target(const float* p) {
-#ifdef RLC_NT_TARGET
     return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-    return *reinterpret_cast<const f32x4*>(p);
-#endif
 }
 __device__ __forceinline__ void st_target(float* p, f32x4 v) {
-#ifdef RLC_NT_TARGET
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
@@ -223,14 +151,6 @@ struct HeadExtra {
     }
 };
 
-// Adam on the small tensors (first layer, a concat layer's extra rows): the hardware-sqrt/rcp form like the big
-// matrices' epilogue unless the build asks for the IEEE-exact expansions
-#ifdef RLC_ADAM_SMALL_EXACT
-#define RLC_ADAM_SMALL adam_step
-#else
-#define RLC_ADAM_SMALL adam_step_fast
-#endif
-
 // MT: M tiles (batch rows / 16); NTW: N tiles per wave (1: widths <= 128, 2: widths <= 256); MSTRIDE: mask row bytes;
 // LERP: target update written (1-tau)*t + tau*w (sac_network.py:72-73) instead of t + tau*(w - t)
 // (hydra_ddpg_network.py:29, naf_network.py:62-63)
@@ -262,9 +182,11 @@ struct Blk {
         if constexpr (TADAM) return adam_step_fast_eps(w, gr, m, v, alpha, adam_eps);
         else return adam_step_fast(w, gr, m, v, alpha);
     }
+    // Adam on the small tensors (first layer, a concat layer's extra rows): the hardware-sqrt/rcp form like the big
+    // matrices' epilogue
     __device__ __forceinline__ float astep_small(float w, float gr, float& m, float& v, float alpha) const {
         if constexpr (TADAM) return adam_step_fast_eps(w, gr, m, v, alpha, adam_eps);
-        else return RLC_ADAM_SMALL(w, gr, m, v, alpha);
+        else return adam_step_fast(w, gr, m, v, alpha);
     }
 #ifdef RLC_STAMPS
     float* stamp_buf = nullptr;
@@ -322,40 +244,14 @@ struct Blk {
     // ---------------------------------------------------------------------------------------
     // hbuf[b][k] = relu(b1[k] + sum_i xs[b][i] W1[i][k])   (rows >= B and columns >= H1 zeroed)
     // ---------------------------------------------------------------------------------------
-    // WP: const float* (the blob in global memory) or const lds_f32* (a copy staged in LDS: stage_load / stage_store)
-    template <class WP>
-    __device__ __forceinline__ void trunk(WP W1, WP b1, const lds_f32* xs) {
+    __device__ __forceinline__ void trunk(const float* W1, const float* b1, const lds_f32* xs) {
         if constexpr (ablate(3)) return;
         if constexpr (WIDE) { trunk_wide(W1, b1, xs); return; }
         if (S <= 4) trunk_t<4>(W1, b1, xs);      // wave-uniform: Pendulum-sized states need one 16-byte read per row
         else trunk_t<SMAX>(W1, b1, xs);
     }
-    // First-layer weights staged in LDS (opt-in, -DRLC_W1_STAGE: measured -0.6 % on DDPG, -1.4 % on SoftActorCritic,
-    // profiles/r03_variant_timings_s6.txt -- the dependent load was not what the passes wait for).  The first layer ([S][H1] + bias, a few KB) is re-read from global memory by
-    // every first-layer pass -- a dependent global load (L2 or HBM latency) in front of a microsecond of arithmetic,
-    // several times per update.  Staged once per update instead: the loads are issued before the minibatch is sampled
-    // and gathered (stage_load: kStage registers per set), stored to LDS behind it (stage_store), and the passes read
-    // [S][H1] weights then [H1] biases from there; a first-layer Adam step that a later pass must see writes its new
-    // values into the LDS copy as well (trunk_grad_adam's `stage` argument).
-    static constexpr int kStage = ((SMAX + 1) * 256 + kThreads - 1) / kThreads;
-    __device__ __forceinline__ void stage_load(float (&r)[kStage], const float* W1, const float* b1) const {
-        const int nw = S * H1, n = nw + H1;
-#pragma unroll
-        for (int j = 0; j < kStage; j++) {
-            const int i = tid + kThreads * j;
-            r[j] = i < nw ? W1[i] : (i < n ? b1[i - nw] : 0.0f);
-        }
-    }
-    __device__ __forceinline__ void stage_store(const float (&r)[kStage], lds_f32* ws) const {
-        const int n = (S + 1) * H1;
-#pragma unroll
-        for (int j = 0; j < kStage; j++) {
-            const int i = tid + kThreads * j;
-            if (i < n) ws[i] = r[j];
-        }
-    }
-    template <int SP, class WP>
-    __device__ __forceinline__ void trunk_t(WP W1, WP b1, const lds_f32* xs) {
+    template <int SP>
+    __device__ __forceinline__ void trunk_t(const float* W1, const float* b1, const lds_f32* xs) {
         // lane = a quad of 4 adjacent columns (its S x 4 weights and 4 biases stay in registers), wave w = rows
         // w, w+8, ...: per row one broadcast read of the state and ONE 16-byte store of four activations
         // (a quarter of the LDS store instructions of the one-column-per-thread form; same i-order per element)
@@ -370,10 +266,7 @@ struct Blk {
                 bias[e] = live ? b1[k] : 0.0f;
             }
             const bool live4[4] = {4 * q < H1, 4 * q + 1 < H1, 4 * q + 2 < H1, 4 * q + 3 < H1};
-#ifndef RLC_TRUNK_UNROLL
-#define RLC_TRUNK_UNROLL 2
-#endif
-#pragma unroll RLC_TRUNK_UNROLL
+#pragma unroll 2
             for (int b = wave; b < MB; b += kWaves) {
                 const f32x4 x0 = *reinterpret_cast<const lds_f32x4*>(&xs[b * SMAX]);
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -395,8 +288,7 @@ struct Blk {
     // registers at a time; between chunks the running sums rest in hbuf, in the very slot their activation ends up in
     // (one lane owns a (row, quad) for every chunk: no barrier, and an fp32 round trip through LDS is exact), so an
     // element is still the i-ascending chain of the narrow form.  State rows: stride xld_for(S), zero beyond S.
-    template <class WP>
-    __device__ __forceinline__ void trunk_wide(WP W1, WP b1, const lds_f32* xs) {
+    __device__ __forceinline__ void trunk_wide(const float* W1, const float* b1, const lds_f32* xs) {
         const int XLD = xld_for(S);
         for (int q = lane; 4 * q < LDH; q += 64) {
             f32x4 bias;
@@ -449,7 +341,7 @@ struct Blk {
     // MT ds_read_b128 + 4*NOWN global_load_dword + 4*MT*NOWN MFMAs and little else.
     // ---------------------------------------------------------------------------------------
     // XMODE (see share_lo): besides its NOWN tiles the wave computes its share of the split tile xt into accx
-    template <int NOWN, int XMODE, bool STREAM = false>
+    template <int NOWN, int XMODE>
     __device__ __forceinline__ void fwd_loop(f32x4 (&acc)[MT][NTW], const float* W, int NT, int KB, bool tail8,
                                              f32x4 (&accx)[MXS], int xt, int xm0) {
         constexpr bool XTRA = XMODE != 0;
@@ -478,7 +370,7 @@ struct Blk {
                 for (int m = 0; m < NX; m++)       // a share shorter than MXS repeats its first tile (result unused)
                     da[m] = *reinterpret_cast<const lds_f32x4*>(xrow(m) + 16 * ch);
 #pragma unroll
-                for (int s2 = 0; s2 < 4; s2++) db[s2] = ld_w<STREAM>(&wpx[(size_t)ch * wstep + 4 * s2]);
+                for (int s2 = 0; s2 < 4; s2++) db[s2] = wpx[(size_t)ch * wstep + 4 * s2];
             }
         };
         auto macX = [&](const f32x4 (&da)[NX], const float (&db)[4]) {
@@ -498,7 +390,7 @@ struct Blk {
 #pragma unroll
             for (int i = 0; i < NOWN; i++)
 #pragma unroll
-                for (int s = 0; s < 4; s++) dst[i][s] = ld_w<STREAM>(&wp[(size_t)ch * wstep + i * tst + 4 * s]);
+                for (int s = 0; s < 4; s++) dst[i][s] = wp[(size_t)ch * wstep + i * tst + 4 * s];
         };
         auto mac = [&](const f32x4 (&a)[MT], const float (&b)[NOWN][4]) {
 #pragma unroll
@@ -613,7 +505,6 @@ struct Blk {
         }
     }
 
-    template <bool STREAM = false>
     __device__ __forceinline__ void fwd_gemm(f32x4 (&acc)[MT][NTW], const float* W, int N, int K) {
         const int NT = (N + 15) >> 4;
 #pragma unroll
@@ -632,14 +523,14 @@ struct Blk {
             if (split_mode(NT)) {                  // workgroup-uniform
 #pragma unroll
                 for (int m = 0; m < MXS; m++) accx[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (T4 && wave == 7) fwd_loop<1, T4 ? 2 : 1, STREAM>(acc, W, NT, KB, tail8, accx, NT - 1, share_lo(3));
-                else if (wave >= 4) fwd_loop<1, 1, STREAM>(acc, W, NT, KB, tail8, accx, NT - 1, share_lo(wave - 4));
-                else fwd_loop<2, 0, STREAM>(acc, W, NT, KB, tail8, accx, 0, 0);
+                if (T4 && wave == 7) fwd_loop<1, T4 ? 2 : 1>(acc, W, NT, KB, tail8, accx, NT - 1, share_lo(3));
+                else if (wave >= 4) fwd_loop<1, 1>(acc, W, NT, KB, tail8, accx, NT - 1, share_lo(wave - 4));
+                else fwd_loop<2, 0>(acc, W, NT, KB, tail8, accx, 0, 0);
                 collect_split<false>(acc, accx);
-            } else if (nown >= 2) fwd_loop<2, 0, STREAM>(acc, W, NT, KB, tail8, accx, 0, 0);
-            else if (nown == 1) fwd_loop<1, 0, STREAM>(acc, W, NT, KB, tail8, accx, 0, 0);
+            } else if (nown >= 2) fwd_loop<2, 0>(acc, W, NT, KB, tail8, accx, 0, 0);
+            else if (nown == 1) fwd_loop<1, 0>(acc, W, NT, KB, tail8, accx, 0, 0);
         } else {
-            if (nown >= 1) fwd_loop<1, 0, STREAM>(acc, W, NT, KB, tail8, accx, 0, 0);
+            if (nown >= 1) fwd_loop<1, 0>(acc, W, NT, KB, tail8, accx, 0, 0);
         }
 #ifdef RLC_STAMPS
         if (lane == 0 && stamp_buf) stamp_buf[48 + wave] += (float)(clock64() - t_w0);   // per-wave k-loop cycles
@@ -653,7 +544,7 @@ struct Blk {
     // registers across the other GEMM's loop (where the compiler spilled it: NAF 224 VGPRs = 0.6 MB of scratch traffic
     // per update).  Same structure and pinning as fwd_loop; summation order per output element unchanged.
     // ---------------------------------------------------------------------------------------
-    template <int NOWN, int XMODE, bool STREAM = false>
+    template <int NOWN, int XMODE>
     __device__ __forceinline__ void fwd_loop2(f32x4 (&accA)[MT][NTW], f32x4 (&accB)[MT][NTW], const float* WA, const float* WB,
                                               int NT, int KB, bool tail8, f32x4 (&accxA)[MXS], f32x4 (&accxB)[MXS], int xt,
                                               int xm0) {
@@ -686,8 +577,8 @@ struct Blk {
                 for (int m = 0; m < NX; m++) da[m] = *reinterpret_cast<const lds_f32x4*>(xrow(m) + 16 * ch);
 #pragma unroll
                 for (int s2 = 0; s2 < 4; s2++) {
-                    db[0][s2] = ld_w<STREAM>(&wpxA[(size_t)ch * wstep + 4 * s2]);
-                    db[1][s2] = ld_w<STREAM>(&wpxB[(size_t)ch * wstep + 4 * s2]);
+                    db[0][s2] = wpxA[(size_t)ch * wstep + 4 * s2];
+                    db[1][s2] = wpxB[(size_t)ch * wstep + 4 * s2];
                 }
             }
         };
@@ -716,8 +607,8 @@ struct Blk {
             for (int i = 0; i < NOWN; i++)
 #pragma unroll
                 for (int s = 0; s < 4; s++) {
-                    dst[0][i][s] = ld_w<STREAM>(&wpA[(size_t)ch * wstep + i * tst + 4 * s]);
-                    dst[1][i][s] = ld_w<STREAM>(&wpB[(size_t)ch * wstep + i * tst + 4 * s]);
+                    dst[0][i][s] = wpA[(size_t)ch * wstep + i * tst + 4 * s];
+                    dst[1][i][s] = wpB[(size_t)ch * wstep + i * tst + 4 * s];
                 }
         };
         auto mac = [&](const f32x4 (&a)[MT], const float (&b)[2][NOWN][4]) {
@@ -826,7 +717,6 @@ struct Blk {
         }
     }
 
-    template <bool STREAM = false>
     __device__ __forceinline__ void fwd_gemm2(f32x4 (&accA)[MT][NTW], f32x4 (&accB)[MT][NTW], const float* WA, const float* WB,
                                               int N, int K) {
         const int NT = (N + 15) >> 4;
@@ -843,16 +733,16 @@ struct Blk {
             if (split_mode(NT)) {
 #pragma unroll
                 for (int m = 0; m < MXS; m++) { accxA[m] = f32x4{0.f, 0.f, 0.f, 0.f}; accxB[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-                if (T4 && wave == 7) fwd_loop2<1, T4 ? 2 : 1, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(3));
-                else if (wave >= 4) fwd_loop2<1, 1, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(wave - 4));
-                else fwd_loop2<2, 0, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
+                if (T4 && wave == 7) fwd_loop2<1, T4 ? 2 : 1>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(3));
+                else if (wave >= 4) fwd_loop2<1, 1>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(wave - 4));
+                else fwd_loop2<2, 0>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
                 collect_split<false>(accA, accxA);
                 __syncthreads();                 // wave 4 has taken the first set out of the hand-off buffer
                 collect_split<false>(accB, accxB);
-            } else if (nown >= 2) fwd_loop2<2, 0, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
-            else if (nown == 1) fwd_loop2<1, 0, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
+            } else if (nown >= 2) fwd_loop2<2, 0>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
+            else if (nown == 1) fwd_loop2<1, 0>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
         } else {
-            if (nown >= 1) fwd_loop2<1, 0, STREAM>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
+            if (nown >= 1) fwd_loop2<1, 0>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
         }
     }
 
@@ -990,38 +880,6 @@ struct Blk {
     __device__ __forceinline__ void store_masks(const f32x4 (&acc)[MT][NTW], int N) {
         if constexpr (ablate(9)) return;
         const int NT = (N + 15) >> 4;
-#ifdef RLC_PACKED_MASKS
-        // (opt-in: measured +-0 on DDPG, -1.4 % on SoftActorCritic, profiles/r03_variant_timings_s6.txt)
-        // One dword store per lane and tile instead of four byte stores (which land four to a bank).  A lane holds the
-        // flags of rows 4g..4g+3 at unit c; a mask dword is four units of one row: the four lanes of a quad (units
-        // 4q..4q+3, same rows) transpose their 4 x 4 bytes with quad-broadcast DPP moves and byte permutes, and lane j of
-        // the quad stores row 4g + j.  (Row stride 4 * odd dwords: the 64 stores of an instruction hit 64 banks.)
-        constexpr unsigned code = BIT == -2 ? 0x38u : 1u << (BIT < 0 ? 0 : BIT);
-        const int r0 = c & 3;
-        const unsigned sel = (unsigned)r0 | ((unsigned)(4 + r0) << 8) | 0x0c0c0000u;     // bytes: lo[r0], hi[r0], 0, 0
-#pragma unroll
-        for (int i = 0; i < NTW; i++) {
-            const int t = tile_of(i);
-            if (t < NT) {
-#pragma unroll
-                for (int mt = 0; mt < MT; mt++) {
-                    unsigned w = 0;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) w |= acc[mt][i][r] > 0.0f ? code << (8 * r) : 0u;
-                    const unsigned w0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0x00, 0xf, 0xf, false);
-                    const unsigned w1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0x55, 0xf, 0xf, false);
-                    const unsigned w2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0xaa, 0xf, 0xf, false);
-                    const unsigned w3 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0xff, 0xf, 0xf, false);
-                    const unsigned lo = __builtin_amdgcn_perm(w1, w0, sel), hi = __builtin_amdgcn_perm(w3, w2, sel);
-                    const unsigned out = lo | (hi << 16);
-                    lds_u32* p = reinterpret_cast<lds_u32*>(&L.mask[(16 * mt + 4 * g + r0) * MSTRIDE + 16 * t + (c & 12)]);
-                    if (OVERWRITE) *p = out;
-                    else *p = (*p & ~(0x01010101u * code)) | out;
-                }
-            }
-        }
-        return;
-#endif
 #pragma unroll
         for (int i = 0; i < NTW; i++) {
             const int t = tile_of(i);
@@ -1105,12 +963,6 @@ struct Blk {
                 dst[i] = *reinterpret_cast<const f32x4*>(wp + i * tst + ((size_t)ch << 8));
             if (XTRA) dx = *reinterpret_cast<const f32x4*>(wpx + ((size_t)ch << 8));
         };
-        // RLC_BWD_PREFETCH: the raw mask dwords of the NEXT chunk are read before the MFMAs of this one (MT registers)
-        unsigned mwn[MT];
-        auto load_masks = [&](int ch) {
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++) mwn[mt] = *reinterpret_cast<const lds_u32*>(mp + brow(mt) * MSTRIDE + 16 * ch);
-        };
         auto mac = [&](const f32x4 (&bin)[NOWN], const f32x4& binx, int ch) {
             f32x4 wv[NS], b[NOWN], bx;
 #pragma unroll
@@ -1121,11 +973,7 @@ struct Blk {
             f32x4 av[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
-#ifdef RLC_BWD_PREFETCH
-                unsigned mw = mwn[mt];
-#else
                 unsigned mw = *reinterpret_cast<const lds_u32*>(mp + brow(mt) * MSTRIDE + 16 * ch);
-#endif
                 if (BIT >= 0) mw = (mw >> (BIT >= 0 ? BIT : 0)) & 0x01010101u;
                 float mf[4];
                 mask4(mw, mf, std::integral_constant<int, BIT>{});
@@ -1142,9 +990,6 @@ struct Blk {
                     }
                 }
             }
-#ifdef RLC_BWD_PREFETCH
-            load_masks(ch + 1 < NTk ? ch + 1 : ch);       // consumed by the next call (clamped on the last chunk)
-#endif
 #pragma unroll
             for (int s = 0; s < 4; s++)
 #pragma unroll
@@ -1176,9 +1021,6 @@ struct Blk {
             }
         };
         loadB(b0, bx0, 0);
-#ifdef RLC_BWD_PREFETCH
-        load_masks(0);
-#endif
         int ch = 0;
         // one scheduling region per pair of chunks (see fwd_loop): next chunk's weight tile first, then per M tile
         // its mask dword read ahead of the 4*NOWN MFMAs that consume the previous one
@@ -1328,20 +1170,19 @@ struct Blk {
     // (LDS [MB][SMAX]).  extra(b, k): further contributions to dL/dh1[b][k] (heads that hang off the first layer).
     // GONLY: only the gradient is produced (written to `tap`, which must not be null); no Adam, no Polyak -- the
     // batch-split kernel (ddpg_split_kernel.h) reduces such partial gradients over the CUs of an agent first.
-    // stage (or null): the LDS copy of this first layer (stage_store layout) that receives the stepped values too
     template <class EXTRA = NoExtra, bool GONLY = false>
     __device__ __forceinline__ void trunk_grad_adam(const f32x4 (&acc)[MT][NTW], float* th, float* m, float* v,
                                                     float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
-                                                    const lds_f32* xs, EXTRA extra = EXTRA{}, lds_f32* stage = nullptr) {
+                                                    const lds_f32* xs, EXTRA extra = EXTRA{}) {
         if constexpr (ablate(7)) return;
         if constexpr (WIDE) { trunk_grad_adam_wide<EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs); return; }
-        if (S <= 4) trunk_grad_adam_t<4, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra, stage);     // wave-uniform
-        else trunk_grad_adam_t<SMAX, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra, stage);
+        if (S <= 4) trunk_grad_adam_t<4, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);     // wave-uniform
+        else trunk_grad_adam_t<SMAX, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);
     }
     template <int SP, class EXTRA, bool GONLY = false>
     __device__ __forceinline__ void trunk_grad_adam_t(const f32x4 (&acc)[MT][NTW], float* th, float* m, float* v,
                                                       float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
-                                                      const lds_f32* xs, EXTRA extra, lds_f32* stage) {
+                                                      const lds_f32* xs, EXTRA extra) {
         const int NT = (H1 + 15) >> 4;
 #pragma unroll
         for (int i = 0; i < NTW; i++) {
@@ -1403,7 +1244,6 @@ struct Blk {
                         const float o = tt ? tt[p] : 0.0f;          // with the other loads: one memory round trip, not two
                         const float nv = astep_small(th[p], gr, mm, vv, alpha);
                         m[p] = mm; v[p] = vv; th[p] = nv;
-                        if (stage) stage[is_bias ? S * H1 + k : s * H1 + k] = nv;
                         if (tap) tap[p] = gr;
                         if (tt) tt[p] = polyak(o, nv, tau);
                     }
@@ -1495,10 +1335,6 @@ struct Blk {
     // already in flight into a second register set.
     // ---------------------------------------------------------------------------------------
     struct WgPre { f32x4 w[4], m[4], v[4], t[4]; };
-    // the first two items of this wave (idx = wave, wave + 8) in flight before wgrad_adam is entered: wgrad_prefetch
-    // issues them ahead of the backward GEMM that precedes the weight-gradient phase, so that their HBM latency hides
-    // under that GEMM instead of under one k-loop (a wave has only two items per matrix at widths <= 128)
-    struct WgPre2 { WgPre a, b; };
 
     // item idx of a [H1 x N] matrix -> N tile t, first M' tile m0, tiles in the chunk nq
     __device__ __forceinline__ void wg_item_geom(int idx, int N, int& t, int& m0, int& nq) const {
@@ -1508,10 +1344,6 @@ struct Blk {
         const int ch = idx / NT;
         nq = cbase + (ch < crem ? 1 : 0);
         m0 = ch * cbase + (ch < crem ? ch : crem);
-    }
-    __device__ __forceinline__ int wg_nitems(int N) const {
-        const int NT = (N + 15) >> 4, NMT = (H1 + 15) >> 4;
-        return NT * ((NMT + 3) >> 2);
     }
     // Prefetch an item's W / m / v / W' NOW (addresses clamped, stores predicated).
     template <bool NOPOL>
@@ -1536,18 +1368,6 @@ struct Blk {
             if constexpr (!NOPOL) P.t[q] = ld_target(&Wt[p]);
         }
     }
-    template <bool NOPOL = false, int NPRE = 2>
-    __device__ __forceinline__ void wgrad_prefetch(WgPre2& pre, int N, const float* Wp, const float* mp, const float* vp,
-                                                   const float* Wt) const {
-        if constexpr (ablate(0) || ablate(1)) return;
-        const int nitems = wg_nitems(N);
-        asm volatile("" ::: "memory");
-        if (wave < nitems) wg_issue<NOPOL>(pre.a, wave, N, Wp, mp, vp, Wt, 0.0f);
-        if constexpr (NPRE > 1)
-            if (wave + kWaves < nitems) wg_issue<NOPOL>(pre.b, wave + kWaves, N, Wp, mp, vp, Wt, 0.0f);
-        asm volatile("" ::: "memory");
-    }
-
     // GONLY: as in trunk_grad_adam -- the gradient tiles go to `tapp` (not null), nothing else is read or written.
     // NOPOL: the matrix has no target copy (Wt unused): no target loads, no Polyak stores.
     template <int NS, int NE, int BIT = -1, bool GONLY = false, bool NOPOL = false>
@@ -1555,15 +1375,6 @@ struct Blk {
                                                int N, float* Wp, float* mp, float* vp,
                                                float alpha, float* tapp, float* Wt, float tau,
                                                const lds_f32* wvec /* LDS [NS][256] */) {
-        WgPre2 none;
-        wgrad_adam_pre<NS, NE, BIT, GONLY, NOPOL, 0>(seed, E, N, Wp, mp, vp, alpha, tapp, Wt, tau, wvec, none);
-    }
-    // NPRE > 0: `pre` holds this wave's first NPRE items already in flight (wgrad_prefetch<NOPOL, NPRE>); by reference and
-    // a compile-time count, so that the registers stay registers
-    template <int NS, int NE, int BIT, bool GONLY, bool NOPOL, int NPRE>
-    __device__ __forceinline__ void wgrad_adam_pre(const lds_f32* seed, const lds_f32* E, int N, float* Wp, float* mp, float* vp,
-                                                   float alpha, float* tapp, float* Wt, float tau, const lds_f32* wvec,
-                                                   WgPre2& pre) {
         if constexpr (ablate(0)) return;
 #ifdef RLC_STAMPS
         const long long t_wg0 = clock64();
@@ -1756,20 +1567,13 @@ struct Blk {
 
         WgPre PA, PB;
         int idx = wave;
-#ifdef RLC_WG_STAGGER
-        // waves 4-7 (the SIMD partners of waves 0-3) start their items late: one wave of a SIMD is then in a k-loop (matrix
-        // pipe) while the other streams an epilogue (memory), instead of both doing the same thing at the same time
-        if (wave >= 4) __builtin_amdgcn_s_sleep(RLC_WG_STAGGER);      // units of 64 cycles
-#endif
         sub_begin();
         // Compiler-level memory barriers pin the prefetch loads and the epilogue stores where they are written:
         // without them hipcc reorders the overlapped prefetch across the stores of the previous item / previous
         // update (K updates in one launch then differ from K launches; tests/test_gpu_ddpg.py pins this).
 #define RLC_CBAR() asm volatile("" ::: "memory")
         RLC_CBAR();
-        bool first = true;
-        if constexpr (NPRE > 0) { PA = pre.a; if constexpr (NPRE > 1) PB = pre.b; }      // already in flight (wgrad_prefetch)
-        else if (idx < nitems) issue(PA, idx);
+        if (idx < nitems) issue(PA, idx);
         sub_stamp(21);
 #ifdef RLC_WG_LATE_ISSUE
         while (idx < nitems) {
@@ -1782,12 +1586,10 @@ struct Blk {
             RLC_CBAR();
             idx += kWaves;
         }
-        (void)first;
 #else
         while (idx < nitems) {
             RLC_CBAR();
-            if (idx + kWaves < nitems && !(NPRE > 1 && first)) issue(PB, idx + kWaves);
-            first = false;
+            if (idx + kWaves < nitems) issue(PB, idx + kWaves);
             RLC_CBAR();
             run_any(PA, idx);
             RLC_CBAR();

@@ -2,7 +2,7 @@
 """Developer loop (CPU box): build ab/<name>.so variants of the BASELINE-shape library that differ in ONE translation
 unit's flags -- the timing-only ablations of mfma_blocks.h (RLC_ABLATE bit masks) or any -D switch -- without touching
 rlcontrol_amd/librlcontrol_hip.so.  The variants are benched on one GPU box by scripts/ab_run.sh.
-    python scripts/ab_ablate.py base abl1=-DRLC_ABLATE=1 wg32=-DRLC_WG_B128 ...
+    python scripts/ab_ablate.py base abl1=-DRLC_ABLATE=1 late=-DRLC_WG_LATE_ISSUE@ddpg_mfma_7_1.o ...
 `name` alone = the unmodified tree.  Units recompiled per variant: ddpg_mfma_inst (7,1), sac_mfma_inst (7,1,1),
 naf_mfma_inst (7,2,2)."""
 import os
