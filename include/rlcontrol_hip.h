@@ -364,7 +364,11 @@ int rlc_naf_update_batch(rlc_naf* h, int32_t agent, int32_t batch, const double*
 /* taps of the last update: 0 Q(s,a), 1 TD target y, 2 V(s) (n = batch); 3 gradient blob (n = P) */
 int rlc_naf_last_tap(rlc_naf* h, int32_t agent, int32_t which, float* dst, int64_t n);
 int rlc_naf_enable_grad_taps(rlc_naf* h, int32_t on);
-/* kernel selection, as rlc_sac_set_kernel: 0 auto, 1 generic, 2 MFMA (S <= 8, A <= 2, widths multiples of 4 in [16,256]) */
+/* kernel selection, as rlc_sac_set_kernel: 0 auto, 1 generic, 2 MFMA.  0 chooses the MFMA kernel at state_dim <= 8,
+ * action_dim <= 2 (no layer norm, layer widths multiples of 4 in [16, 256], batch_size <= 128, LDS <= 160 KiB) and the
+ * generic kernel everywhere else.  2 also takes the wide shapes -- state_dim <= 32, action_dim in {1, 2, 3, 4, 6}, the
+ * other limits as above -- which run on request only; a refusal reads "MFMA NAF kernel does not support these
+ * dimensions: <the limit exceeded>" (the LDS limit with the bytes needed and allowed). */
 int rlc_naf_set_kernel(rlc_naf* h, int32_t variant);
 int rlc_naf_get_kernel(const rlc_naf* h, int32_t* variant_in_use);
 

@@ -89,7 +89,7 @@ _SHARED_KEYS = {
     "SoftActorCritic": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size",
                         "tau", "gamma", "warmup_steps", "norm_type", "exploration_policy", "sample_for_eval", "hip_kernel"),
     "NAF": ("l1_dim", "l2_dim", "batch_size", "buffer_size", "tau", "gamma", "warmup_steps", "norm_type",
-            "exploration_policy"),
+            "exploration_policy", "hip_kernel"),
     "ReverseKL": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size", "tau",
                   "gamma", "warmup_steps", "exploration_policy", "sample_for_eval", "N_param", "l_param", "optim_type",
                   "q_update_type", "use_true_q", "hip_kernel"),
@@ -163,6 +163,13 @@ def _make_population(agent_name, members, arg_params):
         for i, m in enumerate(members):
             pop.set_params(i, init_params(c0.state_dim, c0.action_dim, c0.l1_dim, c0.l2_dim, m[3].random_seed,
                                           c0.norm_type), init_target=True)
+        # optional json key "hip_kernel" as in agents/NAF.py (the device environments' shapes are narrow: "mfma" and
+        # "auto" choose the same kernel there)
+        kernel = getattr(c0, "hip_kernel", "auto")
+        if kernel not in NAFPopulation.KERNEL:
+            raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(NAFPopulation.KERNEL)))
+        if kernel != "auto":
+            pop.set_kernel(kernel)
         return pop
     from rlcontrol_amd.hip_sac import SACPopulation, init_params
     if c0.exploration_policy != 'none' or c0.sample_for_eval == "True" or c0.norm_type == 'none':

@@ -32,6 +32,14 @@ class NAF_Network_Manager(BaseNetwork_Manager):
         theta0 = init_params(config.state_dim, config.action_dim, config.l1_dim, config.l2_dim, config.random_seed,
                              config.norm_type)
         self.population.set_params(0, theta0, init_target=True)
+        # optional json key "hip_kernel": "auto" (the MFMA kernel at state_dim <= 8, action_dim <= 2, else the any-shape
+        # kernel), "generic", or "mfma" -- which also takes state_dim <= 32 with action_dim in {1, 2, 3, 4, 6} (the
+        # reference's Reacher / Hopper / HalfCheetah shapes); a shape it cannot run is refused
+        kernel = getattr(config, "hip_kernel", "auto")
+        if kernel not in NAFPopulation.KERNEL:
+            raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(NAFPopulation.KERNEL)))
+        if kernel != "auto":
+            self.population.set_kernel(kernel)
 
     def device_replay(self):
         return (self.population, 0)

@@ -30,6 +30,8 @@ if FAST:
     SAC_WIDE_VARIANTS = []
 SPLIT_VARIANTS = [(2, 1)] if FAST else [(mt, ad) for ad in (1, 2) for mt in (1, 2, 4)]
 NAF_VARIANTS = [(7, 2, 2)] if FAST else [(mt, ntw, ad) for ad in (1, 2) for ntw in (1, 2) for mt in (2, 4, 7, 8)]
+# the wide form of the NAF kernel (same limits; naf_mfma_kernel.h, WIDE: up to 21 L heads): no tail-of-four units
+NAF_WIDE_VARIANTS = [] if FAST else [(mt, ntw, ad) for ad in (1, 2, 3, 4, 6) for ntw in (1, 2) for mt in (2, 4, 7, 8)]
 # -fgpu-flush-denormals-to-zero: TF-1.15's CPU kernels flush denormals (the reference's checkpoints show it: beta1
 # power exactly 0, idle Adam m slots resting at 9..10 x FLT_MIN; tests/test_ckpt_pins.py) -- the kernels' fp32 VALU
 # arithmetic runs in the same mode
@@ -75,6 +77,9 @@ def _units():
         for flag, tag in t4(mt):
             units.append((os.path.join(CSRC, "naf_mfma_inst.hip"), os.path.join(OBJ, "naf_mfma_%d_%d_%d%s.o" % (mt, ntw, ad, tag)),
                           ["-DRLC_MT=%d" % mt, "-DRLC_NTW=%d" % ntw, "-DRLC_AD=%d" % ad, "-DRLC_T4=%d" % flag]))
+    for mt, ntw, ad in NAF_WIDE_VARIANTS:
+        units.append((os.path.join(CSRC, "naf_mfma_inst.hip"), os.path.join(OBJ, "naf_mfma_w_%d_%d_%d.o" % (mt, ntw, ad)),
+                      ["-DRLC_MT=%d" % mt, "-DRLC_NTW=%d" % ntw, "-DRLC_AD=%d" % ad, "-DRLC_WIDE=1"]))
     return units
 
 
@@ -82,8 +87,9 @@ _LLVM = "/opt/rocm/lib/llvm/bin"
 # Units whose kernels must not carry whole-wave spills (see audit_object); the MFMA kernels are reported, not refused:
 # their SGPR spills sit at phase boundaries and they run two waves per SIMD with the full 256-register budget.
 GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o") + tuple(
-    "ddpg_mfma_w_%d_%d.o" % v for v in MFMA_WIDE_VARIANTS) + tuple(     # the wide DDPG and SAC units are held to the same policy
-    "sac_mfma_w_%d_%d_%d.o" % v for v in SAC_WIDE_VARIANTS)
+    "ddpg_mfma_w_%d_%d.o" % v for v in MFMA_WIDE_VARIANTS) + tuple(     # the wide DDPG, SAC and NAF units are held to the same policy
+    "sac_mfma_w_%d_%d_%d.o" % v for v in SAC_WIDE_VARIANTS) + tuple(
+    "naf_mfma_w_%d_%d_%d.o" % v for v in NAF_WIDE_VARIANTS)
 USAGE_JSON = os.path.join(_HERE, "kernel_resource_usage.json")
 
 

@@ -150,6 +150,35 @@ struct HeadExtra {
         return dh[0] * w[0] + dh[1] * w[1] + dh[2] * w[2] + dh[3] * w[3];
     }
 };
+// The same term for the WIDE first-layer gradient (trunk_grad_adam_wide) with a compile-time head count padded to a
+// multiple of four (NAF at action_dim 1, 2, 3, 4, 6: 1, 3, 6, 10, 21 heads in 4, 4, 8, 12, 24 slots): dhd [MB][NHW], wh
+// [NHW][ldw] with rows sized to the trunk width, both zero beyond the heads in use.  column() reads the column's NHW
+// weights once per N tile, at() the row's gradients in NHW / 4 16-byte reads; the sum runs over the heads in ascending order.
+template <int NHW>
+struct HeadExtraW {
+    static_assert(NHW % 4 == 0, "head slots come in fours");
+    const RLC_LDS float* dhd;
+    const RLC_LDS float* wh;
+    int ldw;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    struct Col { float w[NHW]; };
+    __device__ __forceinline__ Col column(int k) const {
+        Col c;
+#pragma unroll
+        for (int j = 0; j < NHW; j++) c.w[j] = wh[j * ldw + k];
+        return c;
+    }
+    __device__ __forceinline__ float at(const Col& c, int b) const {
+        float e = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NHW / 4; q++) {
+            const f4 dh = *reinterpret_cast<const RLC_LDS f4*>(&dhd[b * NHW + 4 * q]);
+#pragma unroll
+            for (int i = 0; i < 4; i++) e += dh[i] * c.w[4 * q + i];
+        }
+        return e;
+    }
+};
 
 // MT: M tiles (batch rows / 16); NTW: N tiles per wave (1: widths <= 128, 2: widths <= 256); MSTRIDE: mask row bytes;
 // LERP: target update written (1-tau)*t + tau*w (sac_network.py:72-73) instead of t + tau*(w - t)
@@ -1175,9 +1204,12 @@ struct Blk {
                                                     float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
                                                     const lds_f32* xs, EXTRA extra = EXTRA{}) {
         if constexpr (ablate(7)) return;
-        if constexpr (WIDE) { trunk_grad_adam_wide<EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs); return; }
-        if (S <= 4) trunk_grad_adam_t<4, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);     // wave-uniform
-        else trunk_grad_adam_t<SMAX, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);
+        if constexpr (WIDE) {
+            trunk_grad_adam_wide<EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);
+        } else {
+            if (S <= 4) trunk_grad_adam_t<4, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);     // wave-uniform
+            else trunk_grad_adam_t<SMAX, EXTRA, GONLY>(acc, th, m, v, alpha, oW1, ob1, tap, tt, tau, xs, extra);
+        }
     }
     template <int SP, class EXTRA, bool GONLY = false>
     __device__ __forceinline__ void trunk_grad_adam_t(const f32x4 (&acc)[MT][NTW], float* th, float* m, float* v,
@@ -1255,12 +1287,13 @@ struct Blk {
     // WIDE: the same with the state walked in chunks of SMAX inputs, chunk outermost: dh1 of the wave's elements is
     // regenerated per chunk from the live accumulators and the hbuf signs (a select each), so that only one chunk's SMAX
     // column sums are in registers beside the accumulators; every sum over the batch keeps the narrow form's order.  The
-    // bias goes with the last chunk.
+    // bias goes with the last chunk.  EXTRA = NoExtra, or a HeadExtraW (NAF's L heads): dL/dh1[b][k] gains its head term
+    // before the relu select, in every chunk (the column's head weights are read once per N tile).
     template <class EXTRA, bool GONLY>
     __device__ __forceinline__ void trunk_grad_adam_wide(const f32x4 (&acc)[MT][NTW], float* th, float* m, float* v,
                                                          float alpha, int oW1, int ob1, float* tap, float* tt, float tau,
-                                                         const lds_f32* xs) {
-        static_assert(std::is_same<EXTRA, NoExtra>::value, "the wide first-layer gradient has no head term");
+                                                         const lds_f32* xs, EXTRA extra) {
+        constexpr bool HEADS = !std::is_same<EXTRA, NoExtra>::value;
         const int NT = (H1 + 15) >> 4;
         const int XLD = xld_for(S);
 #pragma unroll
@@ -1268,6 +1301,10 @@ struct Blk {
             const int t = tile_of(i);
             if (t >= NT) continue;
             const int k = 16 * t + c;
+            [[maybe_unused]] auto hcol = [&] {
+                if constexpr (HEADS) return extra.column(k < H1 ? k : 0);
+                else return 0;
+            }();
             for (int s0 = 0; s0 < S; s0 += SMAX) {
                 const bool two = s0 + 4 < XLD;
                 float gb = 0.0f;
@@ -1280,7 +1317,9 @@ struct Blk {
                     for (int r = 0; r < 4; r++) {
                         const int b = 16 * mt + 4 * g + r;
                         const float hv = L.hbuf[b * LDH + (k < H1 ? k : 0)];
-                        const float d = (k < H1 && hv > 0.0f) ? acc[mt][i][r] : 0.0f;
+                        float d;
+                        if constexpr (HEADS) d = (k < H1 && hv > 0.0f) ? acc[mt][i][r] + extra.at(hcol, b) : 0.0f;
+                        else d = (k < H1 && hv > 0.0f) ? acc[mt][i][r] : 0.0f;
                         gb += d;
                         const f32x4 x0 = *reinterpret_cast<const lds_f32x4*>(&xs[b * XLD + s0]);
 #pragma unroll

@@ -71,7 +71,12 @@ struct RlcNafRollout;   // naf_rollout_device.h: {RlcNafDev, RlcEnvDev, noise} i
 // rollout (device pointer, may be null): every iteration first takes one environment step of the on-device loop
 int rlc_launch_naf_update(const RlcNafDev& dv, int first_agent, int n_agents, int n_updates, int source,
                           const long long* idx_dev, int grad_taps, hipStream_t st, const RlcNafRollout* rollout = nullptr);
-// MFMA-tiled fused update (dims must satisfy rlc_naf_mfma_supported; tile-blocked layout)
+// MFMA-tiled fused update (tile-blocked layout).  rlc_naf_mfma_refusal: null, or the limit these dimensions exceed (layer
+// norm; widths multiples of 4 in [16, 256]; state_dim <= 32; action_dim in {1,2,3,4,6}; batch_size <= 128; LDS bytes
+// needed against 163,840).  rlc_naf_mfma_supported: the shapes the kernel is the default for (state_dim <= 8, action_dim
+// <= 2) -- above them (rlc_naf_mfma_wide) it runs on request only (rlc_naf_set_kernel), in its wide form.
+inline bool rlc_naf_mfma_wide(const RlcNafDims& d) { return d.S > 8 || d.A > 2; }
+const char* rlc_naf_mfma_refusal(const RlcNafDims& d);
 bool rlc_naf_mfma_supported(const RlcNafDims& d);
 int rlc_launch_naf_update_mfma(const RlcNafDev& dv, int first_agent, int n_agents, int n_updates, int source,
                                const long long* idx_dev, int grad_taps, hipStream_t st, const RlcNafRollout* rollout = nullptr);

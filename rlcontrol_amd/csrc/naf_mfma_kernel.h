@@ -13,7 +13,9 @@
 //   5  weights      GEMM (d Wa2), GEMM (d Wv2) with Adam + Polyak in their epilogues; heads and output layers on VALU
 //
 // 7 contractions of [B, L1] x [L1, L2] per update.  One Adam over every tensor (naf_network.py:54), Polyak by
-// assign_add (:62-63).  Supported shapes: S <= 8, A in {1,2}, L1/L2 multiples of 4 in [16, 128*NTW], B <= 128.
+// assign_add (:62-63).  Supported shapes: S <= 8, A in {1,2}, L1/L2 multiples of 4 in [16, 128*NTW], B <= 128; in the
+// WIDE form (opt-in through rlc_naf_set_kernel, see rlc_naf_mfma_wide) S <= 32 and A in {1,2,3,4,6}, i.e. up to 21 L
+// heads: Blk's WIDE first-layer passes, head rows padded to a multiple of four, a carve of its own (nsmem_carve_wide).
 #pragma once
 #include "mfma_blocks.h"
 #include "naf_common.h"
@@ -42,6 +44,12 @@ struct NSmem {
     lds_i32* dups;
     lds_f32* pol;        // scratch of the on-device training step (naf_rollout_device.h)
     lds_f32x4* xbuf;     // hand-off of the split 13th tile (mfma_blocks.h)
+};
+// what the WIDE form carves on top (a type of its own: the narrow kernel's struct, part of which lives in its stack frame,
+// stays as it is)
+struct NSmemW : NSmem {
+    lds_i32* href;       // [3][NHW] per head: offset of its weight vector, stride between its weights, offset of its bias
+    lds_f32* hb;         // [NHW] the head biases of the update in flight
 };
 
 template <int MSTRIDE>
@@ -79,6 +87,64 @@ __host__ __device__ inline size_t nsmem_carve(const RlcNafDims& d, int MT, lds_u
     return off;
 }
 
+// head slots of the WIDE form: A(A+1)/2 heads padded to a multiple of four (4, 4, 8, 12, 24 at A = 1, 2, 3, 4, 6)
+__host__ __device__ constexpr int naf_nhw(int A) { return (A * (A + 1) / 2 + 3) & ~3; }
+// WIDE: floats between the rows of wh -- the trunk width in whole 16-deep chunks (the head forward reads whole chunks)
+__host__ __device__ inline int naf_ldw(int L1) { return ((L1 + 15) >> 4) << 4; }
+
+// The carve of the WIDE form (rlc_naf_mfma_wide shapes; a function of its own: the narrow carve above stays as it is).
+// State rows lie at stride xld_for(S); hd / dhd rows are naf_nhw(A) wide and wh rows naf_ldw(L1) long.  Three things keep
+// the head-heavy shapes inside the 160 KiB (DESIGN.md 5.4.1 has the barriers):
+//   * dhd IS hd: in phase 3 the thread of sample b reads its row of head pre-activations into registers and then writes
+//     the row's gradients over it; no other thread touches the row in that phase;
+//   * what only the front of an update reads -- x2 (phase-1 trunk), r / g (the y loop), idx / pool / dups (sampler and
+//     gather) -- shares its bytes with what is first written in phase 2 and last read in phase 5: part_a and hd.  Nothing
+//     in that region keeps its zero padding from one update to the next: the gather re-zeroes the tail of every x2 row and
+//     the head forward writes whole hd rows (zeros beyond the heads in use and beyond the minibatch);
+//   * the hand-off buffer of the split 13th tile exists only where a layer has 13 tiles; no scratch of the on-device loop
+//     (`pol`): the WIDE form does not run it.
+template <int MSTRIDE>
+__host__ __device__ inline size_t nsmem_carve_wide(const RlcNafDims& d, int MT, lds_u8* base, NSmemW* out) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        lds_u8* p = base + off;
+        off += (bytes + 15) & ~(size_t)15;
+        return p;
+    };
+    const int MB = MT * 16, A = d.A, LDH = ldh_for(d.L1), XL = xld_for(d.S), NHW = naf_nhw(A), LDW = naf_ldw(d.L1);
+    NSmemW L;
+    L.hbuf = (lds_f32*)take(sizeof(float) * (MB * LDH + 16));
+    L.mask = take((size_t)MB * MSTRIDE);
+    L.part_v = (lds_f32*)take(sizeof(float) * kWaves * MB);
+    L.wvec = (lds_f32*)take(sizeof(float) * (A + 1) * 256);
+    L.wh = (lds_f32*)take(sizeof(float) * NHW * LDW);
+    L.x = (lds_f32*)take(sizeof(float) * MB * XL);
+    L.a = (lds_f32*)take(sizeof(float) * MB * A);
+    L.dz = (lds_f32*)take(sizeof(float) * MB * A);
+    L.y = (lds_f32*)take(sizeof(float) * MB);
+    L.dV = (lds_f32*)take(sizeof(float) * MB);
+    L.href = (lds_i32*)take(sizeof(int) * 3 * NHW);
+    L.hb = (lds_f32*)take(sizeof(float) * NHW);
+    const bool split13 = MSTRIDE == mask_stride(16) && (((d.L1 + 15) >> 4) == 13 || ((d.L2 + 15) >> 4) == 13);
+    L.xbuf = split13 ? (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4)) : nullptr;
+    const size_t shared0 = off;                       // front of the update ...
+    L.x2 = (lds_f32*)take(sizeof(float) * MB * XL);
+    L.r = (lds_f64*)take(sizeof(double) * MB);
+    L.g = (lds_f64*)take(sizeof(double) * MB);
+    L.idx = (lds_i64*)take(sizeof(long long) * RLC_MAX_BATCH);
+    L.pool = (lds_i32*)take(sizeof(int) * 3 * RLC_MAX_BATCH);
+    L.dups = (lds_i32*)take(sizeof(int) * 4);
+    const size_t front_end = off;
+    off = shared0;                                    // ... and phases 2 to 5, over the same bytes
+    L.part_a = (lds_f32*)take(sizeof(float) * kWaves * MB * A);
+    L.hd = (lds_f32*)take(sizeof(float) * MB * NHW);
+    L.dhd = L.hd;
+    if (front_end > off) off = front_end;
+    L.pol = nullptr;
+    if (out) *out = L;
+    return off;
+}
+
 // device offset of head j's weight vector / bias (j < A: diagonal of column j; then column c's below-diagonal entries)
 __device__ __forceinline__ void naf_head_ref(const RlcNafDims& d, int j, int& ow, int& stride, int& ob) {
     if (j < d.A) { ow = d.Wd[j]; stride = 1; ob = d.bd[j]; return; }
@@ -88,22 +154,30 @@ __device__ __forceinline__ void naf_head_ref(const RlcNafDims& d, int j, int& ow
 }
 
 // T4: the minibatch ends within the first four rows of its last tile (mfma_blocks.h, Blk's T4; the launcher checks it)
-template <int MT, int NTW, int AD, bool T4>
+// WIDE: the form for rlc_naf_mfma_wide shapes (Blk's WIDE first-layer passes, up to 21 heads in NHK = naf_nhw(AD) slots,
+// the carve above); the narrow instantiations hold none of its code
+template <int MT, int NTW, int AD, bool T4, bool WIDE = false>
 __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev dv, int first_agent, int n_updates,
                                                                        int source, const long long* host_idx,
                                                                        int grad_taps, const RlcNafRollout* rollout) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int MSTRIDE = mask_stride(8 * NTW);
     constexpr int NN = AD * (AD - 1) / 2, NH = AD + NN;
-    static_assert(NH <= NHP, "head count");
-    using U = Blk<MT, NTW, MSTRIDE, false, false, T4>;
+    constexpr int NHK = WIDE ? naf_nhw(AD) : NHP;       // floats per row of hd / dhd
+    static_assert(NH <= NHK, "head count");
+    static_assert(WIDE || AD <= 2, "more than two action columns: the WIDE form");
+    static_assert(!(WIDE && T4), "the WIDE form has no tail-of-four units");
+    using U = Blk<MT, NTW, MSTRIDE, false, false, T4, WIDE>;
     constexpr int MB = U::MB;
     const RlcNafDims d = dv.d;
     U u;
     u.init_geometry();
     u.S = d.S; u.H1 = d.L1; u.B = d.B; u.LDH = ldh_for(d.L1);
-    NSmem L;
-    nsmem_carve<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
+    const int XL = WIDE ? xld_for(d.S) : SMAX;          // floats between state rows in LDS
+    const int LDW = WIDE ? naf_ldw(d.L1) : 256;         // floats between the rows of wh
+    typename std::conditional<WIDE, NSmemW, NSmem>::type L;
+    if constexpr (WIDE) nsmem_carve_wide<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
+    else nsmem_carve<MSTRIDE>(d, MT, (lds_u8*)smem, &L);
     u.L.hbuf = L.hbuf; u.L.mask = L.mask; u.L.xbuf = L.xbuf;
     const int tid = u.tid, S = d.S, L1 = d.L1, L2 = d.L2, B = d.B, LDH = u.LDH;
     const int agent = first_agent + blockIdx.x;
@@ -127,10 +201,24 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
 
     // zero the padded tails of the per-sample vectors once (rows >= B never change afterwards)
     for (int i = tid; i < MB * AD; i += kThreads) { L.a[i] = 0.f; L.dz[i] = 0.f; }
-    for (int i = tid; i < MB * NHP; i += kThreads) { L.hd[i] = 0.f; L.dhd[i] = 0.f; }
-    for (int i = tid; i < MB * SMAX; i += kThreads) { L.x[i] = 0.f; L.x2[i] = 0.f; }
-    for (int i = tid; i < MB; i += kThreads) { L.y[i] = 0.f; L.dV[i] = 0.f; }
-    for (int i = tid; i < NHP * 256; i += kThreads) L.wh[i] = 0.f;
+    if constexpr (WIDE) {
+        // x2 and hd / dhd share their bytes with other arrays (nsmem_carve_wide): their padding is rewritten every update
+        for (int i = tid; i < MB * XL; i += kThreads) L.x[i] = 0.f;
+        for (int i = tid; i < NHK * LDW; i += kThreads) L.wh[i] = 0.f;
+        // every head's offsets, resolved once (naf_head_ref walks the columns)
+        for (int j = tid; j < NHK; j += kThreads) {
+            int ow = 0, st = 0, ob = 0;
+            if (j < NH) naf_head_ref(d, j, ow, st, ob);
+            L.href[j] = ow; L.href[NHK + j] = st; L.href[2 * NHK + j] = ob;
+            L.hb[j] = 0.f;
+        }
+        for (int i = tid; i < MB; i += kThreads) { L.y[i] = 0.f; L.dV[i] = 0.f; }
+    } else {
+        for (int i = tid; i < MB * NHP; i += kThreads) { L.hd[i] = 0.f; L.dhd[i] = 0.f; }
+        for (int i = tid; i < MB * SMAX; i += kThreads) { L.x[i] = 0.f; L.x2[i] = 0.f; }
+        for (int i = tid; i < MB; i += kThreads) { L.y[i] = 0.f; L.dV[i] = 0.f; }
+        for (int i = tid; i < NHP * 256; i += kThreads) L.wh[i] = 0.f;
+    }
     for (int i = tid; i < MB * MSTRIDE / 4; i += kThreads) reinterpret_cast<lds_u32*>(L.mask)[i] = 0u;
     if (tid < 16) L.hbuf[MB * LDH + tid] = 0.0f;
     __syncthreads();
@@ -157,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
         if (tid == 0) t_prev = clock64();
 #endif
         asm volatile("" : "+v"(u.c), "+v"(u.g), "+s"(u.wave));     // see ddpg_mfma_kernel.h
-        if (rollout) {
+        if (!WIDE && rollout) {
             // on-device experiment loop: one environment step first; update when learn() would run
             if (!rlc_naf_train_step_device(rollout, agent, (float*)L.pol)) continue;
         }
@@ -184,9 +272,11 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
                 L.r[b] = dv.rep.rr[slot]; L.g[b] = dv.rep.rg[slot];
             }
             for (int i = 0; i < S; i++) {
-                L.x[b * SMAX + i] = clip_state_val(ps[i], dv.clip_state, dv.smin[i], dv.smax[i]);
-                L.x2[b * SMAX + i] = clip_state_val(ps2[i], dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x[b * XL + i] = clip_state_val(ps[i], dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x2[b * XL + i] = clip_state_val(ps2[i], dv.clip_state, dv.smin[i], dv.smax[i]);
             }
+            if constexpr (WIDE)
+                for (int i = S; i < XL; i++) L.x2[b * XL + i] = 0.0f;       // part_a has been over these bytes
 #pragma unroll
             for (int j = 0; j < AD; j++) L.a[b * AD + j] = pa[j];
         }
@@ -213,16 +303,58 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
             const int j = i / 256, n = i % 256;
             L.wvec[i] = n < L2 ? (j < AD ? th[d.Wa3 + n * AD + j] : th[d.Wv3 + n]) : 0.0f;
         }
-        for (int i = tid; i < NH * 256; i += kThreads) {
-            const int j = i / 256, k = i % 256;
-            int ow, st, ob;
-            naf_head_ref(d, j, ow, st, ob);
-            L.wh[i] = k < L1 ? th[ow + k * st] : 0.0f;
+        if constexpr (WIDE) {
+            for (int i = tid; i < NH * LDW; i += kThreads) {
+                const int j = i / LDW, k = i - j * LDW;
+                L.wh[i] = k < L1 ? th[L.href[j] + k * L.href[NHK + j]] : 0.0f;
+            }
+            if (tid < NH) L.hb[tid] = th[L.href[2 * NHK + tid]];
+        } else {
+            for (int i = tid; i < NH * 256; i += kThreads) {
+                const int j = i / 256, k = i % 256;
+                int ow, st, ob;
+                naf_head_ref(d, j, ow, st, ob);
+                L.wh[i] = k < L1 ? th[ow + k * st] : 0.0f;
+            }
         }
         __syncthreads();
         // L heads from the trunk image: wave w < MT takes batch tile w; lane (c, g) sums k = 16 ch + 4 g .. + 3 of row
         // 16 w + c; the four lane groups are combined in a fixed order
-        if (u.wave < MT) {
+        if constexpr (WIDE) {
+            // NH sums per lane; lane group 0 then writes the WHOLE row of NHK floats, zeros beyond the heads in use and in
+            // the rows beyond the minibatch (the row's bytes held r / g / idx before: nsmem_carve_wide)
+            if (u.wave < MT) {
+                const int row = 16 * u.wave + u.c;
+                const lds_f32* hp = L.hbuf + row * LDH + 4 * u.g;
+                const lds_f32* wp = L.wh + 4 * u.g;
+                float hs[NH];
+#pragma unroll
+                for (int j = 0; j < NH; j++) hs[j] = 0.0f;
+                const int KB = (L1 + 15) >> 4;
+                for (int ch = 0; ch < KB; ch++) {
+                    const f32x4 hv = *reinterpret_cast<const lds_f32x4*>(hp + 16 * ch);
+#pragma unroll
+                    for (int j = 0; j < NH; j++) {
+                        const f32x4 wj = *reinterpret_cast<const lds_f32x4*>(wp + j * LDW + 16 * ch);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) hs[j] += hv[e] * wj[e];
+                    }
+                }
+                float o[NHK];
+#pragma unroll
+                for (int j = 0; j < NHK; j++) o[j] = 0.0f;
+#pragma unroll
+                for (int j = 0; j < NH; j++) {
+                    const float s = col4_sum(hs[j]);
+                    o[j] = row < B ? s + L.hb[j] : 0.0f;
+                }
+                if (u.g == 0) {
+#pragma unroll
+                    for (int q = 0; q < NHK / 4; q++)
+                        *reinterpret_cast<lds_f32x4*>(&L.hd[row * NHK + 4 * q]) = f32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+                }
+            }
+        } else if (u.wave < MT) {
             const lds_f32* hp = L.hbuf + (16 * u.wave + u.c) * LDH + 4 * u.g;
             float hs[NH];
 #pragma unroll
@@ -268,9 +400,9 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
                 ddiff[j] = 0.0f;
             }
             const float V = u.template part_sum<1>(L.part_v, b, 0) + th[d.bv3];
-            float hdv[NHP];
+            float hdv[NHK];
 #pragma unroll
-            for (int j = 0; j < NH; j++) hdv[j] = L.hd[b * NHP + j];
+            for (int j = 0; j < NH; j++) hdv[j] = L.hd[b * NHK + j];      // (WIDE: dhd below is written over this row)
             float p[AD], l0[AD];
             float adv = 0.0f;
             int off = 0;
@@ -297,9 +429,9 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
 #pragma unroll
                 for (int k = 1; k < AD - c; k++) ddiff[c + k] += dp * hdv[AD + off + k - 1];
                 const float xpre = hdv[c];
-                L.dhd[b * NHP + c] = (xpre >= -5.0f && xpre <= 5.0f) ? dp * diff[c] * l0[c] : 0.0f;
+                L.dhd[b * NHK + c] = (xpre >= -5.0f && xpre <= 5.0f) ? dp * diff[c] * l0[c] : 0.0f;
 #pragma unroll
-                for (int k = 1; k < AD - c; k++) L.dhd[b * NHP + AD + off + k - 1] = dp * diff[c + k];
+                for (int k = 1; k < AD - c; k++) L.dhd[b * NHK + AD + off + k - 1] = dp * diff[c + k];
                 off += AD - 1 - c;
             }
 #pragma unroll
@@ -357,36 +489,66 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
         __syncthreads();
         // heads off the trunk: dL/dh1[b][k] += sum_j dhd[b][j] * wh[j][k]  (dhd / wh rows beyond the NH heads in use are zero)
         STAMP();
-        u.trunk_grad_adam(acc, th, mm, vv, alpha, d.W1, d.b1, tapg, tt, tau, L.x, HeadExtra{L.dhd, L.wh});
+        if constexpr (WIDE) u.trunk_grad_adam(acc, th, mm, vv, alpha, d.W1, d.b1, tapg, tt, tau, L.x, HeadExtraW<NHK>{L.dhd, L.wh, LDW});
+        else u.trunk_grad_adam(acc, th, mm, vv, alpha, d.W1, d.b1, tapg, tt, tau, L.x, HeadExtra{L.dhd, L.wh});
         STAMP();
         // head weights: g[k][j] = sum_b h1[b][k] dhd[b][j] (thread k), head biases (wave j)
-        for (int k = tid; k < L1; k += kThreads) {
-            float gs[NH];
+        if constexpr (WIDE) {
+            for (int k = tid; k < L1; k += kThreads) {
+                float gs[NH];
 #pragma unroll
-            for (int j = 0; j < NH; j++) gs[j] = 0.0f;
-            for (int b = 0; b < B; b++) {
-                const float hv = L.hbuf[b * LDH + k];
-                const f32x4 dh = *reinterpret_cast<const lds_f32x4*>(&L.dhd[b * NHP]);
+                for (int j = 0; j < NH; j++) gs[j] = 0.0f;
+                for (int b = 0; b < B; b++) {
+                    const float hv = L.hbuf[b * LDH + k];
 #pragma unroll
-                for (int j = 0; j < NH; j++) gs[j] += hv * dh[j];
+                    for (int q = 0; q < NHK / 4; q++) {
+                        const f32x4 dh = *reinterpret_cast<const lds_f32x4*>(&L.dhd[b * NHK + 4 * q]);
+#pragma unroll
+                        for (int e = 0; e < 4; e++)
+                            if (4 * q + e < NH) gs[4 * q + e] += hv * dh[e];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < NH; j++)
+                    U::adam_scalar(th, mm, vv, tt, tapg, L.href[j] + k * L.href[NHK + j], gs[j], alpha, tau);
             }
+            // up to 21 head biases over the eight waves in rounds: wave j mod 8
+            for (int j = u.wave; j < NH; j += kWaves) {
+                float gr = 0.0f;
+                for (int b = u.lane; b < MB; b += 64) gr += L.dhd[b * NHK + j];
 #pragma unroll
-            for (int j = 0; j < NH; j++) {
-                int ow, st, ob;
-                naf_head_ref(d, j, ow, st, ob);
-                U::adam_scalar(th, mm, vv, tt, tapg, ow + k * st, gs[j], alpha, tau);
+                for (int off = 32; off > 0; off >>= 1) gr += __shfl_xor(gr, off, 64);
+                if (u.lane == 0) U::adam_scalar(th, mm, vv, tt, tapg, L.href[2 * NHK + j], gr, alpha, tau);
             }
-        }
-        if (u.wave < NH) {
-            const int j = u.wave;
-            float gr = 0.0f;
-            for (int b = u.lane; b < MB; b += 64) gr += L.dhd[b * NHP + j];
+        } else {
+            for (int k = tid; k < L1; k += kThreads) {
+                float gs[NH];
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) gr += __shfl_xor(gr, off, 64);
-            if (u.lane == 0) {
-                int ow, st, ob;
-                naf_head_ref(d, j, ow, st, ob);
-                U::adam_scalar(th, mm, vv, tt, tapg, ob, gr, alpha, tau);
+                for (int j = 0; j < NH; j++) gs[j] = 0.0f;
+                for (int b = 0; b < B; b++) {
+                    const float hv = L.hbuf[b * LDH + k];
+                    const f32x4 dh = *reinterpret_cast<const lds_f32x4*>(&L.dhd[b * NHP]);
+#pragma unroll
+                    for (int j = 0; j < NH; j++) gs[j] += hv * dh[j];
+                }
+#pragma unroll
+                for (int j = 0; j < NH; j++) {
+                    int ow, st, ob;
+                    naf_head_ref(d, j, ow, st, ob);
+                    U::adam_scalar(th, mm, vv, tt, tapg, ow + k * st, gs[j], alpha, tau);
+                }
+            }
+            if (u.wave < NH) {
+                const int j = u.wave;
+                float gr = 0.0f;
+                for (int b = u.lane; b < MB; b += 64) gr += L.dhd[b * NHP + j];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) gr += __shfl_xor(gr, off, 64);
+                if (u.lane == 0) {
+                    int ow, st, ob;
+                    naf_head_ref(d, j, ow, st, ob);
+                    U::adam_scalar(th, mm, vv, tt, tapg, ob, gr, alpha, tau);
+                }
             }
         }
         STAMP();
@@ -432,14 +594,18 @@ __global__ __launch_bounds__(kThreads) void rlc_naf_update_mfma_kernel(RlcNafDev
 #undef STAMP
 }
 
-template <int MT, int NTW, int AD, bool T4>
+template <int MT, int NTW, int AD, bool T4, bool WIDE = false>
 int naf_launch_t(const RlcNafDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
                  int grad_taps, hipStream_t st, const RlcNafRollout* rollout) {
     constexpr int MSTRIDE = mask_stride(8 * NTW);
-    const size_t lds = nsmem_carve<MSTRIDE>(dv.d, MT, nullptr, nullptr);
+    const size_t lds = WIDE ? nsmem_carve_wide<MSTRIDE>(dv.d, MT, nullptr, nullptr) : nsmem_carve<MSTRIDE>(dv.d, MT, nullptr, nullptr);
     RLC_REQUIRE(lds <= 160 * 1024, "MFMA NAF kernel needs %zu B of LDS (> 160 KiB)", lds);
     RLC_REQUIRE(!T4 || rlc_tail4(dv.d.B, MT), "tail-of-four kernel launched for batch %d", dv.d.B);
-    auto kern = rlc_naf_update_mfma_kernel<MT, NTW, AD, T4>;
+    RLC_REQUIRE(WIDE == rlc_naf_mfma_wide(dv.d), "state_dim %d / action_dim %d on the %s form of the MFMA NAF kernel", dv.d.S,
+                dv.d.A, WIDE ? "wide" : "narrow");
+    RLC_REQUIRE(!(WIDE && rollout), "the on-device experiment loop runs the narrow MFMA kernel (state_dim <= 8, action_dim <= 2)");
+    RLC_REQUIRE(dv.d.B <= 16 * MT, "batch %d does not fit %d batch tiles", dv.d.B, MT);
+    auto kern = rlc_naf_update_mfma_kernel<MT, NTW, AD, T4, WIDE>;
     static bool attr_set = false;
     if (!attr_set) {
         RLC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -4,7 +4,6 @@
 int rlc_h_naf_launch_update(rlc_handle* h, int first, int n, int n_updates, int source, const long long* idx_dev,
                             const RlcNafRollout* rollout) {
     if (rlc_h_variant(h) == 2) {
-        RLC_REQUIRE(rlc_naf_mfma_supported(h->naf.d), "MFMA NAF kernel does not support these dimensions");
         return rlc_launch_naf_update_mfma(h->naf, first, n, n_updates, source, idx_dev, h->grad_taps, h->st, rollout);
     }
     return rlc_launch_naf_update(h->naf, first, n, n_updates, source, idx_dev, h->grad_taps, h->st, rollout);
@@ -107,8 +106,10 @@ int rlc_naf_update_batch(rlc_handle* h, int32_t agent, int32_t batch, const doub
 }
 
 int rlc_naf_set_kernel(rlc_handle* h, int32_t variant) {
+    // 2 also takes the wide shapes (state_dim <= 32, action_dim in {1,2,3,4,6}), which 0 leaves on the any-shape kernel
+    const char* why = h && h->algo == RLC_ALGO_NAF && variant == 2 ? rlc_naf_mfma_refusal(h->naf.d) : nullptr;
     return rlc_h_set_kernel(h, RLC_ALGO_NAF, variant,
-                            h && !rlc_naf_mfma_supported(h->naf.d) ? "MFMA NAF kernel does not support these dimensions" : "");
+                            why ? std::string("MFMA NAF kernel does not support these dimensions: ") + why : std::string());
 }
 int rlc_naf_get_kernel(const rlc_handle* h, int32_t* variant_in_use) { return rlc_h_get_kernel(h, RLC_ALGO_NAF, variant_in_use); }
 int rlc_naf_enable_grad_taps(rlc_handle* h, int32_t on) { return rlc_h_enable_grad_taps(h, RLC_ALGO_NAF, on); }

@@ -46,6 +46,9 @@ def init_params(S, A, L1, L2, seed, norm_type="input_norm"):
 
 
 class NAFPopulation(Population):
+    """set_kernel("auto") (the default of a new population) runs the MFMA kernel at state_dim <= 8, action_dim <= 2 and
+    the any-shape kernel elsewhere; set_kernel("mfma") also takes state_dim <= 32 with action_dim in {1, 2, 3, 4, 6} (the
+    wide form, on request only) and raises RlcError naming the limit for anything else."""
     PREFIX = "rlc_naf"
     BETA_POWERS = 2
     BLOB = {"theta": 0, "theta_target": 1, "adam_m": 2, "adam_v": 3}
