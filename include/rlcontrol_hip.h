@@ -56,7 +56,9 @@ typedef struct rlc_ddpg_config {
     int32_t norm_type;       /* RLC_NORM_NONE: config.norm_type 'none' / 'input_norm' (activation only);
                               * RLC_NORM_LAYER: 'layer' -- tf.contrib.layers.layer_norm(center, scale) before every
                               * hidden relu (agents/network/base_network.py:53-56); each layer adds beta then gamma to
-                              * the blob.  'batch' (base_network.py:57-59) is not implemented: create fails. */
+                              * the blob.  A new handle runs 'layer' on the any-shape kernel; rlc_ddpg_set_kernel(h, 2)
+                              * moves the hydra network at state_dim <= 8, action_dim <= 2 to the MFMA kernel's
+                              * layer-norm form.  'batch' (base_network.py:57-59) is not implemented: create fails. */
     float tau;               /* config.tau */
     float reserved1;
     const float* state_min;  /* [state_dim] */
@@ -149,7 +151,9 @@ int rlc_ddpg_update_batch(rlc_ddpg* h, int32_t agent, int32_t batch, const doubl
  *  [16, 256], batch_size <= 128, LDS <= 160 KiB) and the generic kernel everywhere else.  2 also takes the wide shapes
  *  -- state_dim <= 32, action_dim in {1, 2, 3, 4, 6}, the other limits as above -- which run on request only; a refusal
  *  reads "MFMA kernel does not support these dimensions: <the limit exceeded>" (the LDS limit with the bytes needed and
- *  allowed).  Either switch re-packs weights and optimizer state; acting, qval and the replay work in both layouts. */
+ *  allowed).  2 also takes norm_type 'layer' (on request only as well): the hydra network at state_dim <= 8, action_dim
+ *  <= 2, whose two activation images need more LDS (200-wide layers: batch_size <= 64); not with separate_networks,
+ *  latency mode or the on-device loop.  Either switch re-packs weights and optimizer state; acting, qval and the replay work in both layouts. */
 int rlc_ddpg_set_kernel(rlc_ddpg* h, int32_t variant);
 int rlc_ddpg_get_kernel(const rlc_ddpg* h, int32_t* variant_in_use);
 /* latency mode (no reference counterpart): split every agent's minibatch over n_workgroups CUs (1 = off, at most 8;

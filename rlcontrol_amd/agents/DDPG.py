@@ -49,7 +49,9 @@ class DDPG_Network_Manager(BaseNetwork_Manager):
             norm_type=config.norm_type, separate_networks=separate)
         # optional json key "hip_kernel": "auto" (the MFMA kernel at state_dim <= 8, action_dim <= 2, else the any-shape
         # kernel), "generic", or "mfma" -- which also takes state_dim <= 32 with action_dim in {1, 2, 3, 4, 6} (the
-        # reference's Reacher / Hopper / HalfCheetah / Swimmer / LunarLander shapes); a shape it cannot run is refused
+        # reference's Reacher / Hopper / HalfCheetah / Swimmer / LunarLander shapes) and norm_type 'layer' on the hydra
+        # network at state_dim <= 8, action_dim <= 2 (ddpg_layer.json: "auto" keeps it on the any-shape kernel); a shape
+        # it cannot run is refused
         kernel = getattr(config, "hip_kernel", "auto")
         if kernel != "auto":
             self.population.set_kernel(kernel)

@@ -18,6 +18,8 @@ PLAIN = ("rlc_api.hip", "rlc_api_sac.hip", "rlc_api_naf.hip", "replay_kernels.hi
 MFMA_VARIANTS = [(mt, ad) for ad in (1, 2) for mt in (2, 4, 7, 8)]
 # the wide form of the DDPG kernel (state_dim <= 32, action_dim in {1,2,3,4,6}; ddpg_mfma_kernel.h, WIDE): no tail-of-four units
 MFMA_WIDE_VARIANTS = [(mt, ad) for ad in (1, 2, 3, 4, 6) for mt in (2, 4, 7, 8)]
+# the layer-norm form of the DDPG kernel (ddpg_ln_mfma_kernel.h: the hydra network, state_dim <= 8, action_dim <= 2)
+MFMA_LN_VARIANTS = [(mt, ad) for ad in (1, 2) for mt in (2, 4, 7, 8)]
 FAST = os.environ.get("RLC_FAST_BUILD", "0") == "1"     # developer loop: only the headline shape
 SAC_VARIANTS = [(mt, ntw, ad) for ad in (1, 2) for ntw in (1, 2) for mt in (2, 4, 7, 8)]
 # the wide form of the SoftActorCritic kernel (same limits; sac_mfma_kernel.h, WIDE): no tail-of-four units, and no
@@ -26,6 +28,7 @@ SAC_WIDE_VARIANTS = [(mt, ntw, ad) for ad in (1, 2, 3, 4, 6) for ntw in (1, 2) f
 if FAST:
     MFMA_VARIANTS = [(7, 1)]
     MFMA_WIDE_VARIANTS = []
+    MFMA_LN_VARIANTS = []
     SAC_VARIANTS = [(7, 1, 1)]
     SAC_WIDE_VARIANTS = []
 SPLIT_VARIANTS = [(2, 1)] if FAST else [(mt, ad) for ad in (1, 2) for mt in (1, 2, 4)]
@@ -63,6 +66,9 @@ def _units():
     for mt, ad in MFMA_WIDE_VARIANTS:
         units.append((os.path.join(CSRC, "ddpg_mfma_inst.hip"), os.path.join(OBJ, "ddpg_mfma_w_%d_%d.o" % (mt, ad)),
                       ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad, "-DRLC_WIDE=1"]))
+    for mt, ad in MFMA_LN_VARIANTS:
+        units.append((os.path.join(CSRC, "ddpg_ln_mfma_inst.hip"), os.path.join(OBJ, "ddpg_mfma_ln_%d_%d.o" % (mt, ad)),
+                      ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad]))
     for mt, ad in SPLIT_VARIANTS:
         units.append((os.path.join(CSRC, "ddpg_split_inst.hip"), os.path.join(OBJ, "ddpg_split_%d_%d.o" % (mt, ad)),
                       ["-DRLC_MT=%d" % mt, "-DRLC_AD=%d" % ad]))
@@ -88,6 +94,7 @@ _LLVM = "/opt/rocm/lib/llvm/bin"
 # their SGPR spills sit at phase boundaries and they run two waves per SIMD with the full 256-register budget.
 GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o") + tuple(
     "ddpg_mfma_w_%d_%d.o" % v for v in MFMA_WIDE_VARIANTS) + tuple(     # the wide DDPG, SAC and NAF units are held to the same policy
+    "ddpg_mfma_ln_%d_%d.o" % v for v in MFMA_LN_VARIANTS) + tuple(      # ... and the layer-norm DDPG units
     "sac_mfma_w_%d_%d_%d.o" % v for v in SAC_WIDE_VARIANTS) + tuple(
     "naf_mfma_w_%d_%d_%d.o" % v for v in NAF_WIDE_VARIANTS)
 USAGE_JSON = os.path.join(_HERE, "kernel_resource_usage.json")

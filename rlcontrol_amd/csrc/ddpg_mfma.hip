@@ -3,6 +3,7 @@
 #include <cstdio>
 
 #include "ddpg_mfma_kernel.h"
+#include "ddpg_ln_mfma_kernel.h"
 
 #ifdef RLC_ONLY_7_1   // developer loop (RLC_FAST_BUILD=1): only the headline shape is compiled
 #define RLC_FOR_V2(X) X(7, 1)
@@ -35,13 +36,22 @@ RLC_FOR_T4(RLC_DECLT4)
     int rlc_mfma_launch_w_##M##_##A_(const RlcDev&, int, int, int, int, const long long*, int, hipStream_t, const RlcRollout*, int);
 RLC_FOR_W(RLC_DECLW)
 
+// the layer-norm form (ddpg_ln_mfma_kernel.h): the hydra network at state_dim <= 8, action_dim <= 2; no tail-of-four units,
+// no on-device loop
+#ifdef RLC_ONLY_7_1
+#define RLC_FOR_LN(X)
+#else
+#define RLC_FOR_LN(X) X(2, 1) X(4, 1) X(7, 1) X(8, 1) X(2, 2) X(4, 2) X(7, 2) X(8, 2)
+#endif
+#define RLC_DECLLN(M, A_) int rlc_mfma_launch_ln_##M##_##A_(const RlcDev&, int, int, int, int, const long long*, int, hipStream_t);
+RLC_FOR_LN(RLC_DECLLN)
+
 static inline int mt_for(int B) { return B <= 32 ? 2 : (B <= 64 ? 4 : (B <= 112 ? 7 : 8)); }
 
 static const size_t kLdsLimit = 160 * 1024;
 
 // why the MFMA kernel (either form) cannot run these dimensions, or null; the text names the limit
 const char* rlc_mfma_refusal(const RlcDims& d) {
-    if (d.norm) return "norm_type 'layer' runs on the any-shape kernel";
     auto okdim = [](int h) { return h >= 16 && h <= 256 && (h % 4) == 0; };
     if (!(okdim(d.H1) && okdim(d.HA) && okdim(d.HC))) return "the MFMA kernel needs layer widths that are multiples of 4 in [16, 256]";
     if (d.S < 1 || d.S > SWIDE) return "the MFMA kernel needs state_dim <= 32";
@@ -50,7 +60,16 @@ const char* rlc_mfma_refusal(const RlcDims& d) {
 #ifdef RLC_ONLY_7_1
     if (rlc_mfma_wide(d)) return "this build holds the headline shape's MFMA kernel only (state_dim <= 8, action_dim 1)";
 #endif
-    const size_t lds = rlc_mfma_wide(d) ? smem_carve<true>(d, mt_for(d.B), nullptr, nullptr)
+    if (d.norm) {
+        // the layer-norm form: opt-in like the wide form (rlc_mfma_supported stays false for it)
+        if (d.sep) return "norm_type 'layer' with network 'separate' runs on the any-shape kernel";
+        if (rlc_mfma_wide(d)) return "norm_type 'layer' on the MFMA kernel needs state_dim <= 8 and action_dim <= 2";
+#ifdef RLC_ONLY_7_1
+        return "this build holds no MFMA kernel for norm_type 'layer'";
+#endif
+    }
+    const size_t lds = d.norm ? smem_carve_ln(d, mt_for(d.B), nullptr, nullptr)
+                       : rlc_mfma_wide(d) ? smem_carve<true>(d, mt_for(d.B), nullptr, nullptr)
                                         : smem_carve<false>(d, mt_for(d.B), nullptr, nullptr);
     if (lds > kLdsLimit) {
         static thread_local char msg[160];
@@ -62,8 +81,9 @@ const char* rlc_mfma_refusal(const RlcDims& d) {
 }
 
 // The shapes the MFMA kernel is the DEFAULT for (rlc_ddpg_create, the `auto` variant, latency mode, the device loop):
-// state_dim <= 8, action_dim <= 2.  The wide form runs on request only (rlc_ddpg_set_kernel).
-bool rlc_mfma_supported(const RlcDims& d) { return !rlc_mfma_wide(d) && rlc_mfma_refusal(d) == nullptr; }
+// state_dim <= 8, action_dim <= 2, no layer norm.  The wide form and the layer-norm form run on request only
+// (rlc_ddpg_set_kernel).
+bool rlc_mfma_supported(const RlcDims& d) { return !d.norm && !rlc_mfma_wide(d) && rlc_mfma_refusal(d) == nullptr; }
 
 int rlc_launch_ddpg_update_mfma(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source,
                                 const long long* idx_dev, int grad_taps, hipStream_t st, const RlcRollout* rollout,
@@ -72,6 +92,15 @@ int rlc_launch_ddpg_update_mfma(const RlcDev& dv, int first_agent, int n_agents,
     RLC_REQUIRE(!why, "MFMA kernel does not support these dimensions: %s", why);
     RLC_REQUIRE(dv.d.blocked, "the MFMA kernel reads tile-blocked weights (rlc_ddpg_set_kernel re-packs them)");
     const int mt = mt_for(dv.d.B);
+    if (dv.d.norm) {
+        RLC_REQUIRE(!rollout, "the on-device experiment loop runs norm_type 'layer' on the any-shape kernel");
+#define RLC_CASELN(M, A_)         \
+    if (mt == M && dv.d.A == A_) return rlc_mfma_launch_ln_##M##_##A_(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st);
+        RLC_FOR_LN(RLC_CASELN)
+#undef RLC_CASELN
+        rlc_set_error("no layer-norm MFMA instantiation for MT=%d A=%d in this build", mt, dv.d.A);
+        return 3;
+    }
     if (rlc_mfma_wide(dv.d)) {
         RLC_REQUIRE(!rollout, "the on-device experiment loop runs the narrow MFMA kernel (state_dim <= 8, action_dim <= 2)");
 #define RLC_CASEW(M, A_)          \

@@ -49,7 +49,9 @@ def init_params(S, A, H1, HA, HC, seed, norm_type="input_norm", separate_network
 class DDPGPopulation(Population):
     """set_kernel("auto") (the default of a new population) runs the MFMA kernel at state_dim <= 8, action_dim <= 2 and
     the any-shape kernel elsewhere; set_kernel("mfma") also takes state_dim <= 32 with action_dim in {1, 2, 3, 4, 6} (the
-    wide form, on request only) and raises RlcError naming the limit for anything else."""
+    wide form, on request only) and norm_type 'layer' (the hydra network at state_dim <= 8, action_dim <= 2; on request
+    only: a new layer-norm population runs the any-shape kernel, and 200-wide layers fit up to batch_size 64), and raises
+    RlcError naming the limit for anything else."""
     PREFIX = "rlc_ddpg"
     BLOB = {"theta": 0, "theta_target": 1, "actor_m": 2, "actor_v": 3, "critic_m": 4, "critic_v": 5}
     TAP = {"q": 0, "y": 1, "a_out": 2, "dqda": 3, "grads_c": 4, "grads_a": 5}
