@@ -152,8 +152,12 @@ int rlc_ddpg_update_batch(rlc_ddpg* h, int32_t agent, int32_t batch, const doubl
  *  -- state_dim <= 32, action_dim in {1, 2, 3, 4, 6}, the other limits as above -- which run on request only; a refusal
  *  reads "MFMA kernel does not support these dimensions: <the limit exceeded>" (the LDS limit with the bytes needed and
  *  allowed).  2 also takes norm_type 'layer' (on request only as well): the hydra network at state_dim <= 8, action_dim
- *  <= 2, whose two activation images need more LDS (200-wide layers: batch_size <= 64); not with separate_networks,
- *  latency mode or the on-device loop.  Either switch re-packs weights and optimizer state; acting, qval and the replay work in both layouts. */
+ *  <= 2, whose two activation images need more LDS (200-wide layers: batch_size <= 64); not with separate_networks or
+ *  latency mode.  The on-device loop (rlc_ddpg_rollout_*) runs whichever kernel is in use when rlc_ddpg_rollout_create
+ *  is called, the layer-norm form included.  Either switch re-packs weights and optimizer state; acting, qval and the
+ *  replay work in both layouts.  With a rollout attached the only switch left is the one back to the generic kernel
+ *  (1, or 0 where 0 means the generic kernel): a call that would put the MFMA kernel in use, or keep it, fails with
+ *  "the kernel variant cannot change once a rollout is attached to the handle". */
 int rlc_ddpg_set_kernel(rlc_ddpg* h, int32_t variant);
 int rlc_ddpg_get_kernel(const rlc_ddpg* h, int32_t* variant_in_use);
 /* latency mode (no reference counterpart): split every agent's minibatch over n_workgroups CUs (1 = off, at most 8;

@@ -85,7 +85,7 @@ def _run_data(random_seed, env_json, result):
 # per-agent learning rates / entropy scale and the seed)
 _SHARED_KEYS = {
     "DDPG": ("shared_l1_dim", "actor_l2_dim", "critic_l2_dim", "batch_size", "buffer_size", "tau", "gamma",
-             "warmup_steps", "norm_type", "network", "exploration_policy", "ou_theta", "ou_mu", "ou_sigma"),
+             "warmup_steps", "norm_type", "network", "exploration_policy", "ou_theta", "ou_mu", "ou_sigma", "hip_kernel"),
     "SoftActorCritic": ("actor_l1_dim", "actor_l2_dim", "critic_l1_dim", "critic_l2_dim", "batch_size", "buffer_size",
                         "tau", "gamma", "warmup_steps", "norm_type", "exploration_policy", "sample_for_eval", "hip_kernel"),
     "NAF": ("l1_dim", "l2_dim", "batch_size", "buffer_size", "tau", "gamma", "warmup_steps", "norm_type",
@@ -149,6 +149,13 @@ def _make_population(agent_name, members, arg_params):
         for i, m in enumerate(members):
             pop.set_params(i, init_params(c0.state_dim, c0.action_dim, c0.shared_l1_dim, c0.actor_l2_dim,
                                           c0.critic_l2_dim, m[3].random_seed, c0.norm_type, separate), init_target=True)
+        # optional json key "hip_kernel" as in agents/DDPG.py ("mfma" is the only way to the layer-norm form of that
+        # kernel; a shape it does not take is refused here, before the rollout is attached and any step runs)
+        kernel = getattr(c0, "hip_kernel", "auto")
+        if kernel not in DDPGPopulation.KERNEL:
+            raise ValueError("hip_kernel %r: expected one of %s" % (kernel, sorted(DDPGPopulation.KERNEL)))
+        if kernel != "auto":
+            pop.set_kernel(kernel)
         return pop
     if agent_name == "NAF":
         from rlcontrol_amd.hip_naf import NAFPopulation, init_params

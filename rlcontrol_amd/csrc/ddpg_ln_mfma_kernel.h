@@ -25,7 +25,13 @@
 //                            a GEMM), then ln_bwd_rows and the first-layer column pass
 //
 // Scope: the hydra network (d.sep == 0), S <= 8, A <= 2, widths multiples of 4 in [16, 256], batch <= 128; the two-pass
-// forward (no FUSE), the padded last tile (no tail-of-four), no on-device loop.
+// forward (no FUSE), the padded last tile (no tail-of-four).
+//
+// On-device experiment loop: with a rollout attached, one training step (rlc_train_step_device) opens every iteration of
+// the update loop, as in rlc_ddpg_update_mfma_kernel.  That kernel lends the step its activation image; here both images,
+// `stat` and the per-sample vectors are zeroed ONCE per launch and their rows >= B / columns >= N are relied on to stay
+// zero, so the step gets the stretch of LDS from `part` to the end of `idx` instead (ln_step_scratch_floats): every float
+// of it is written before it is read in every update, and none of its padding is ever read.
 #pragma once
 #include "ddpg_mfma_kernel.h"
 
@@ -87,6 +93,16 @@ __host__ __device__ inline size_t smem_carve_ln(const RlcDims& d, int MT, lds_u8
     else L.xbuf = nullptr;
     if (out) *out = L;
     return off;
+}
+
+// LDS lent to the on-device training step: `part`, `r`, `g` and `idx`, contiguous in the carve above.  All four are dead
+// at the top of an update and nobody relies on what they hold past their live rows: row_reduce / row_dot store every
+// (wave, row) partial that row_stat / part_sum read; the gather stores r[b], g[b] and the sampler (or the host-index copy)
+// idx[b] for every b < B, and nothing reads them at b >= B.  16 MB + 4 MB + 2 RLC_MAX_BATCH floats (MB = 16 MT): 896 at two
+// tiles, against at most 564 the step needs (ddpg_policy_lds_floats + 4 at 256-wide layers).
+__host__ __device__ inline size_t ln_step_scratch_floats(int MT) {
+    const size_t MB = (size_t)MT * 16;
+    return (sizeof(float) * kWaves * MB * 2 + 2 * sizeof(double) * MB + sizeof(long long) * RLC_MAX_BATCH) / sizeof(float);
 }
 
 __device__ __forceinline__ float ln_wave_sum(float v) {
@@ -595,7 +611,8 @@ struct LnBlk : Blk<MT, NTW, MSTRIDE> {
 template <int MT, int AD>
 __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_ln_mfma_kernel(RlcDev dv, int first_agent, int n_updates,
                                                                            int source, const long long* host_idx,
-                                                                           int grad_taps) {
+                                                                           int grad_taps, const RlcRollout* rollout,
+                                                                           int q8_first) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using U = LnBlk<MT>;
     static_assert(AD <= 2, "the layer-norm form takes action_dim <= 2");
@@ -721,6 +738,12 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_ln_mfma_kernel(RlcDe
         // re-materialise lane geometry every update (ddpg_mfma_kernel.h: keeps the address arithmetic of the phases from
         // being hoisted out of the update loop and spilled)
         asm volatile("" : "+v"(u.c), "+v"(u.g), "+s"(u.wave));
+        if (rollout) {
+            // on-device experiment loop: one environment step first; the update runs when learn() would
+            // (agents/base_agent.py:65-70).  The step's scratch is part .. idx (ln_step_scratch_floats), not an image:
+            // it writes nothing that this launch zeroed once; it opens and ends behind a barrier.
+            if (!rlc_train_step_device(rollout, agent, (float*)L.part, upd == 0 ? q8_first : 0)) continue;
+        }
         // ================= sample + gather (utils/replaybuffer.py:32-37) =================
         const RlcRingMeta ring = dv.rep.ring[agent];
         if (source == RLC_SRC_REPLAY_DEVICE_SAMPLER) {
@@ -966,19 +989,30 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_ln_mfma_kernel(RlcDe
 
 template <int MT, int AD>
 int launch_ln(const RlcDev& dv, int first_agent, int n_agents, int n_updates, int source, const long long* idx_dev,
-              int grad_taps, hipStream_t st) {
+              int grad_taps, hipStream_t st, const RlcRollout* rollout, int q8_first) {
     const size_t lds = smem_carve_ln(dv.d, MT, nullptr, nullptr);
     RLC_REQUIRE(lds <= 160 * 1024, "layer-norm MFMA DDPG kernel needs %zu B of LDS (> 160 KiB)", lds);
     RLC_REQUIRE(dv.d.norm && !dv.d.sep && !rlc_mfma_wide(dv.d) && dv.d.A == AD && dv.d.B <= 16 * MT,
                 "layer-norm MFMA DDPG kernel launched for dimensions it does not take");
     RLC_REQUIRE(dv.scratch && dv.scratch_stride >= (long long)dv.d.B * dv.d.H1, "layer-norm MFMA DDPG kernel needs the population's scratch");
+    {
+        // the carve must still hold part, r, g and idx back to back, and the stretch must hold the training step's scratch
+        SmemLn L;
+        smem_carve_ln(dv.d, MT, nullptr, &L);
+        const size_t have = (size_t)((lds_u8*)L.idx - (lds_u8*)L.part) + sizeof(long long) * RLC_MAX_BATCH;
+        const size_t need = sizeof(float) * (ddpg_policy_lds_floats(dv.d) + 4);
+        RLC_REQUIRE(!rollout || (have == sizeof(float) * ln_step_scratch_floats(MT) && need <= have),
+                    "layer-norm MFMA DDPG kernel: the on-device training step needs %zu B of LDS scratch, %zu B lie between the "
+                    "row partials and the sample indices", need, have);
+    }
     auto kern = rlc_ddpg_update_ln_mfma_kernel<MT, AD>;
     static bool attr_set = false;
     if (!attr_set) {
         RLC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
-    hipLaunchKernelGGL(kern, dim3(n_agents), dim3(kThreads), lds, st, dv, first_agent, n_updates, source, idx_dev, grad_taps);
+    hipLaunchKernelGGL(kern, dim3(n_agents), dim3(kThreads), lds, st, dv, first_agent, n_updates, source, idx_dev, grad_taps,
+                       rollout, q8_first);
     RLC_HIP(hipGetLastError());
     return 0;
 }

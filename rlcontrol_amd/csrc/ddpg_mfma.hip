@@ -36,14 +36,15 @@ RLC_FOR_T4(RLC_DECLT4)
     int rlc_mfma_launch_w_##M##_##A_(const RlcDev&, int, int, int, int, const long long*, int, hipStream_t, const RlcRollout*, int);
 RLC_FOR_W(RLC_DECLW)
 
-// the layer-norm form (ddpg_ln_mfma_kernel.h): the hydra network at state_dim <= 8, action_dim <= 2; no tail-of-four units,
-// no on-device loop
+// the layer-norm form (ddpg_ln_mfma_kernel.h): the hydra network at state_dim <= 8, action_dim <= 2; no tail-of-four units;
+// the on-device loop as the narrow form has it (a runtime pointer, not units of its own)
 #ifdef RLC_ONLY_7_1
 #define RLC_FOR_LN(X)
 #else
 #define RLC_FOR_LN(X) X(2, 1) X(4, 1) X(7, 1) X(8, 1) X(2, 2) X(4, 2) X(7, 2) X(8, 2)
 #endif
-#define RLC_DECLLN(M, A_) int rlc_mfma_launch_ln_##M##_##A_(const RlcDev&, int, int, int, int, const long long*, int, hipStream_t);
+#define RLC_DECLLN(M, A_) \
+    int rlc_mfma_launch_ln_##M##_##A_(const RlcDev&, int, int, int, int, const long long*, int, hipStream_t, const RlcRollout*, int);
 RLC_FOR_LN(RLC_DECLLN)
 
 static inline int mt_for(int B) { return B <= 32 ? 2 : (B <= 64 ? 4 : (B <= 112 ? 7 : 8)); }
@@ -93,9 +94,10 @@ int rlc_launch_ddpg_update_mfma(const RlcDev& dv, int first_agent, int n_agents,
     RLC_REQUIRE(dv.d.blocked, "the MFMA kernel reads tile-blocked weights (rlc_ddpg_set_kernel re-packs them)");
     const int mt = mt_for(dv.d.B);
     if (dv.d.norm) {
-        RLC_REQUIRE(!rollout, "the on-device experiment loop runs norm_type 'layer' on the any-shape kernel");
 #define RLC_CASELN(M, A_)         \
-    if (mt == M && dv.d.A == A_) return rlc_mfma_launch_ln_##M##_##A_(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st);
+    if (mt == M && dv.d.A == A_)  \
+        return rlc_mfma_launch_ln_##M##_##A_(dv, first_agent, n_agents, n_updates, source, idx_dev, grad_taps, st, rollout, \
+                                             q8_first);
         RLC_FOR_LN(RLC_CASELN)
 #undef RLC_CASELN
         rlc_set_error("no layer-norm MFMA instantiation for MT=%d A=%d in this build", mt, dv.d.A);

@@ -800,8 +800,15 @@ int rlc_ddpg_update_batch(rlc_handle* h, int32_t agent, int32_t batch, const dou
 int rlc_ddpg_set_kernel(rlc_handle* h, int32_t variant) {
     // 2 also takes the wide shapes (state_dim <= 32, action_dim in {1,2,3,4,6}), which 0 leaves on the any-shape kernel
     const char* why = h && h->algo == RLC_ALGO_DDPG && variant == 2 ? rlc_mfma_refusal(h->dv.d) : nullptr;
-    return rlc_h_set_kernel(h, RLC_ALGO_DDPG, variant,
-                            why ? std::string("MFMA kernel does not support these dimensions: ") + why : std::string());
+    // With a rollout attached the handle can still go back to the generic kernel: the blobs are re-packed and the device
+    // copy of the views, which holds the weight layout, is written again.  A call that would put (or keep) the MFMA kernel
+    // in use stays refused: the kernel is chosen before rlc_ddpg_rollout_create.
+    const bool to_generic = h && h->algo == RLC_ALGO_DDPG && (variant == 1 || (variant == 0 && !rlc_mfma_supported(h->dv.d)));
+    if (int rc = rlc_h_set_kernel(h, RLC_ALGO_DDPG, variant,
+                                  why ? std::string("MFMA kernel does not support these dimensions: ") + why : std::string(),
+                                  !to_generic))
+        return rc;
+    return h->has_env ? rlc_h_upload_ddpg_rollout(h) : 0;
 }
 
 int rlc_ddpg_get_kernel(const rlc_handle* h, int32_t* variant_in_use) {

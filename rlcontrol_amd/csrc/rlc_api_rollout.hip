@@ -17,6 +17,16 @@ static int launch_steps(rlc_handle* h, int n, int q8_first) {
                                           h->rollout_dev, q8_first);
 }
 
+int rlc_h_upload_ddpg_rollout(rlc_handle* h) {
+    if (rlc_h_use_device(h)) return 1;
+    RlcRollout ro;
+    ro.dv = h->dv;
+    ro.env = h->env;
+    RLC_HIP(hipMemcpyAsync(h->rollout_dev, &ro, sizeof(ro), hipMemcpyHostToDevice, h->st));
+    RLC_HIP(hipStreamSynchronize(h->st));          // `ro` is a stack variable
+    return 0;
+}
+
 extern "C" {
 
 // environment state, bookkeeping and logs of a population (any algorithm)
@@ -66,12 +76,7 @@ int rlc_ddpg_rollout_create(rlc_handle* h, const rlc_rollout_config* cfg) {
     RLC_NEED(h, RLC_ALGO_DDPG);
     if (rollout_alloc(h, cfg)) return 1;
     // device-resident argument block of the fused launches
-    if (rlc_h_malloc(h, &h->rollout_dev, 1)) return 1;
-    RlcRollout ro;
-    ro.dv = h->dv;
-    ro.env = h->env;
-    RLC_HIP(hipMemcpyAsync(h->rollout_dev, &ro, sizeof(ro), hipMemcpyHostToDevice, h->st));
-    RLC_HIP(hipStreamSynchronize(h->st));
+    if (rlc_h_malloc(h, &h->rollout_dev, 1) || rlc_h_upload_ddpg_rollout(h)) return 1;
     h->has_env = true;
     return 0;
 }

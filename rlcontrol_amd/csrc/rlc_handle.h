@@ -163,6 +163,9 @@ int rlc_h_enable_grad_taps(rlc_handle* h, int algo, int on);
 int rlc_h_last_tap(rlc_handle* h, int algo, int agent, int which, float* dst, int64_t n);
 // re-pack every blob between the row-major and the tile-blocked layout (a kernel switch changes the weight layout)
 int rlc_h_relayout(rlc_handle* h, int blocked);
+// (re)write the device copy of a DDPG handle's views {dv, env}, the argument block of the fused step launches: when the
+// rollout is created, and when a kernel switch has changed dv (the weight layout) with a rollout attached
+int rlc_h_upload_ddpg_rollout(rlc_handle* h);
 // set_kernel: argument checks (mfma_refusal: why variant 2 cannot run, empty if it can), then the re-pack
 int rlc_h_set_kernel(rlc_handle* h, int algo, int variant, const std::string& mfma_refusal, bool refuse_rollout = true);
 int rlc_h_get_kernel(const rlc_handle* h, int algo, int32_t* variant_in_use);
