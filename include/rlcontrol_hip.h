@@ -380,6 +380,60 @@ int rlc_naf_enable_grad_taps(rlc_naf* h, int32_t on);
 int rlc_naf_set_kernel(rlc_naf* h, int32_t variant);
 int rlc_naf_get_kernel(const rlc_naf* h, int32_t* variant_in_use);
 
+
+/* ===================================== OptimalQ ====================================================
+ * The Q-learner without an actor that the bimodal study uses as its yardstick (agents/OptimalQ.py:11-94,
+ * agents/network/optimal_q_network.py:6-196; jsonfiles/agent/optimalq.json): the greedy action and the TD target's
+ * max_a' Q'(s', a') come from an exhaustive search over a discretised action grid (optimal_q_network.py:121-161).
+ * Parameter blob, variable creation order (optimal_q_network.py:82-108): W1[S][L1] b1 | W2[L1+A][L2] b2 | W3[L2] b3,
+ * the action rows last in W2.   blob selector: 0 theta, 1 target, 2 Adam m, 3 Adam v.
+ * The grid is built on the host (optimal_q_network.py:163-179: np.arange over the FIRST dimension's bounds, the same
+ * axis for every dimension, np.meshgrid in its default 'xy' order) and uploaded once as fp32.  Any batch_size the
+ * other any-shape kernels accept is accepted (the reference raises for anything but 32 and 1, :134-139). */
+typedef rlc_handle rlc_optq;
+#define RLC_OPTQ_MAX_NODES (1 << 24)
+typedef struct rlc_optq_config {
+    int32_t device, n_agents, state_dim, action_dim;   /* action_dim <= 6 */
+    int32_t l1_dim, l2_dim;                             /* jsonfiles/agent/optimalq.json */
+    int32_t batch_size, clip_state;                     /* clip_state: norm_type != 'none' (optimal_q_network.py:75-76) */
+    int64_t buffer_size;
+    float tau;
+    int32_t norm_type;           /* RLC_NORM_NONE ('none' / 'input_norm') only: 'layer' and 'batch' are refused */
+    const float* state_min;      /* [state_dim] */
+    const float* state_max;
+    const float* learning_rate;  /* [n_agents] (optimal_q_network.py:8,57) */
+    const uint64_t* seed;        /* [n_agents] Philox keys of the device sampler */
+    int32_t n_nodes;             /* 1 .. RLC_OPTQ_MAX_NODES grid nodes */
+    int32_t reserved0;
+    const float* node_actions;   /* [n_nodes][action_dim] discretized_action_pairs (optimal_q_network.py:163-179) */
+} rlc_optq_config;
+
+int rlc_optq_create(const rlc_optq_config* cfg, rlc_optq** out);          /* optimal_q_network.py:7-65 */
+int rlc_optq_param_count(const rlc_optq* h, int64_t* out_p);
+int rlc_optq_set_blob(rlc_optq* h, int32_t agent, int32_t which, const float* src, int64_t n);
+int rlc_optq_get_blob(rlc_optq* h, int32_t agent, int32_t which, float* dst, int64_t n);
+int rlc_optq_get_beta_powers(rlc_optq* h, int32_t agent, float* pw2);
+int rlc_optq_init_target(rlc_optq* h, int32_t agent);                     /* optimal_q_network.py:60-61,187-188 */
+/* get_max_action(use_target=False) (optimal_q_network.py:121-161, agents/OptimalQ.py:28-30): out_action [n][A] =
+ * the grid row of the largest online Q (the lowest index among equal maxima, as np.argmax); out_q (may be NULL) [n] */
+int rlc_optq_act(rlc_optq* h, int32_t first_agent, int32_t n, const double* states, float* out_action, float* out_q);
+/* queued / fetched as rlc_ddpg_act_queue / rlc_ddpg_act_fetch (the host adds the exploration noise after the fetch) */
+int rlc_optq_act_queue(rlc_optq* h, int32_t first_agent, int32_t n, const double* states);
+int rlc_optq_act_fetch(rlc_optq* h, int32_t first_agent, int32_t n, float* out_action, float* out_q);
+/* BaseAgent.learn for every agent: sample_batch + OptimalQ_Network_Manager.update_network (agents/OptimalQ.py:68-89) */
+int rlc_optq_update(rlc_optq* h, int32_t n_updates, const int64_t* host_indices);
+int rlc_optq_update_batch(rlc_optq* h, int32_t agent, int32_t batch, const double* states, const double* actions,
+                          const double* next_states, const double* rewards, const double* gammas);
+/* taps of the last update: 0 Q(s,a), 1 TD target y, 2 max_a' Q'(s',a') (n = batch); 3 the grid row that attains it
+ * (n = batch * action_dim); 4 gradient blob (n = P) */
+int rlc_optq_last_tap(rlc_optq* h, int32_t agent, int32_t which, float* dst, int64_t n);
+int rlc_optq_enable_grad_taps(rlc_optq* h, int32_t on);
+/* predict Q(s,a) rows on one agent's online network (optimal_q_network.py:193-196) */
+int rlc_optq_qval(rlc_optq* h, int32_t agent, int32_t n, const double* states, const double* actions, float* out_q);
+/* 0 auto and 1 generic both mean the any-shape kernel; 2 is refused: "OptimalQ runs on the any-shape kernel only" */
+int rlc_optq_set_kernel(rlc_optq* h, int32_t variant);
+int rlc_optq_get_kernel(const rlc_optq* h, int32_t* variant_in_use);
+
 /* ---------------------------------------------------------------------------------------------------
  * On-device experiment loop: Experiment.run of the reference
  * (experiment.py:52-217) for every agent of a DDPG population, with the environment simulated on the GPU.

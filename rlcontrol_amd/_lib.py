@@ -34,6 +34,9 @@ EXPORTS = (
     "rlc_naf_create", "rlc_naf_param_count", "rlc_naf_set_blob", "rlc_naf_get_blob", "rlc_naf_get_beta_powers",
     "rlc_naf_init_target", "rlc_naf_act", "rlc_naf_act_queue", "rlc_naf_act_fetch", "rlc_naf_update", "rlc_naf_update_batch", "rlc_naf_last_tap",
     "rlc_naf_enable_grad_taps", "rlc_naf_set_kernel", "rlc_naf_get_kernel",
+    "rlc_optq_create", "rlc_optq_param_count", "rlc_optq_set_blob", "rlc_optq_get_blob", "rlc_optq_get_beta_powers",
+    "rlc_optq_init_target", "rlc_optq_act", "rlc_optq_act_queue", "rlc_optq_act_fetch", "rlc_optq_update", "rlc_optq_update_batch",
+    "rlc_optq_last_tap", "rlc_optq_enable_grad_taps", "rlc_optq_qval", "rlc_optq_set_kernel", "rlc_optq_get_kernel",
     "rlc_ddpg_rollout_create", "rlc_ddpg_rollout_run", "rlc_sac_rollout_create", "rlc_sac_rollout_run", "rlc_kl_rollout_create", "rlc_kl_rollout_run",
     "rlc_naf_rollout_create", "rlc_naf_rollout_run", "rlc_rollout_counts", "rlc_rollout_train_log",
     "rlc_rollout_eval_log", "rlc_rollout_observation",
@@ -101,6 +104,19 @@ class rlc_naf_config(ctypes.Structure):
         ("state_min", ctypes.POINTER(ctypes.c_float)), ("state_max", ctypes.POINTER(ctypes.c_float)),
         ("action_max", ctypes.POINTER(ctypes.c_float)), ("learning_rate", ctypes.POINTER(ctypes.c_float)),
         ("seed", ctypes.POINTER(ctypes.c_uint64)), ("action_min", ctypes.POINTER(ctypes.c_float)),
+    ]
+
+
+class rlc_optq_config(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("state_dim", ctypes.c_int32),
+        ("action_dim", ctypes.c_int32), ("l1_dim", ctypes.c_int32), ("l2_dim", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32), ("clip_state", ctypes.c_int32), ("buffer_size", ctypes.c_int64),
+        ("tau", ctypes.c_float), ("norm_type", ctypes.c_int32),
+        ("state_min", ctypes.POINTER(ctypes.c_float)), ("state_max", ctypes.POINTER(ctypes.c_float)),
+        ("learning_rate", ctypes.POINTER(ctypes.c_float)), ("seed", ctypes.POINTER(ctypes.c_uint64)),
+        ("n_nodes", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("node_actions", ctypes.POINTER(ctypes.c_float)),
     ]
 
 

@@ -14,6 +14,7 @@ _AGENTS = {
     "NAF": ("rlcontrol_amd.agents.NAF", "NAF"),
     "ReverseKL": ("rlcontrol_amd.agents.ReverseKL", "ReverseKL"),
     "ForwardKL": ("rlcontrol_amd.agents.ForwardKL", "ForwardKL"),
+    "OptimalQ": ("rlcontrol_amd.agents.OptimalQ", "OptimalQ"),
 }
 
 
