@@ -31,8 +31,10 @@ struct Smem {
     lds_i32* pool;
     lds_i32* dups;
     lds_f32x4* xbuf;    // hand-off of the split 13th tile (mfma_blocks.h)
-    lds_f32 *w1t, *w1o; // always null (the retired staged-first-layer experiment): part of the struct's image
-                        // in scratch -- taking them out moves the kernel's scratch offsets, so a change of its own
+    lds_f32* partq;     // [kWaves][MB] the target critic's q' partials: a buffer of their own in the narrow carve (they are
+                        // summed in the dq phase, after the critic's q partials have taken `part`); WIDE: = part
+    lds_f32* w1o;       // always null (the retired staged-first-layer experiment): part of the struct's image
+                        // in scratch -- taking it out moves the kernel's scratch offsets, so a change of its own
 };
 
 // shapes that only the WIDE form of the kernel takes: a state row above SMAX floats or more than two action columns
@@ -86,7 +88,9 @@ __host__ __device__ inline size_t smem_carve(const RlcDims& d, int MT, lds_u8* b
     } else {
         L.xbuf = (lds_f32x4*)take(sizeof(float) * 4 * 64 * (MT - (MT + 3) / 4));
     }
-    L.w1t = L.w1o = nullptr;
+    if constexpr (wide) L.partq = L.part;
+    else L.partq = (lds_f32*)take(sizeof(float) * kWaves * MB);
+    L.w1o = nullptr;
     if (out) *out = L;
     return off;
 }
@@ -226,7 +230,8 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         // epilogue (the action rows): one k-loop for both hidden contractions when the two layers have one width
         // (mfma_blocks.h fwd_gemm2; +0.9 % at the BASELINE shape, profiles/r03_variant_timings_s9.txt)
         f32x4 acc2[MT][NTW];
-        if constexpr (fuse_fwd) u.fwd_gemm2(acc, acc2, tt + d.oWa2, tt + d.oWc2, HA, H1);
+        // (narrow form: the ragged 13th tiles of the pair packed into one tile where they are at most half full)
+        if constexpr (fuse_fwd) u.template fwd_gemm2<!WIDE>(acc, acc2, tt + d.oWa2, tt + d.oWc2, HA, H1);
         else u.fwd_gemm(acc, tt + d.oWa2, HA, H1);
         u.template bias_relu<0>(acc, tt + d.oba2, HA);
         u.template row_dot<false, AD>(acc, HA, [&](int n, int j) { return tt[d.oWa3 + n * AD + j]; }, L.part);   // z' partials
@@ -251,17 +256,27 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             u.fwd_gemm(acc, tt + d.oWc2, HC, H1);
         }
         u.template bias_relu<AD>(acc, tt + d.obc2, HC, L.aout, tt + d.oWc2, d.arow0);
-        u.template row_dot<false, 1>(acc, HC, [&](int n, int) { return tt[d.oWc3 + n]; }, L.part);      // q' partials
-        __syncthreads();
-        STAMP();
-        for (int b = tid; b < B; b += kThreads) {
-            const float qt = u.template part_sum<1>(L.part, b, 0) + tt[d.obc3];
-            const float y = (float)(L.r[b] + L.g[b] * (double)qt);     // float64 TD glue (DDPG.py:80-84)
-            L.y[b] = y;
-            dv.tap_y[(size_t)agent * RLC_MAX_BATCH + b] = y;
+        u.template row_dot<false, 1>(acc, HC, [&](int n, int) { return tt[d.oWc3 + n]; }, L.partq);     // q' partials
+        // Narrow form, fused pair: the q' partials rest in a buffer of their own until the dq phase sums them into the TD
+        // target -- no phase (and no barrier pair) for the B threads that do it.  Every wave has left the pair's k-loop
+        // (the barriers around a'), so the critic's first layer may overwrite the trunk image now.  (Without the fused
+        // pair the target critic's own k-loop has just read that image: the barrier stays.)
+        constexpr bool td_in_dq = !WIDE && fuse_fwd;
+        if constexpr (!td_in_dq) {
+            __syncthreads();
+            STAMP();
+            for (int b = tid; b < B; b += kThreads) {
+                const float qt = u.template part_sum<1>(L.partq, b, 0) + tt[d.obc3];
+                const float y = (float)(L.r[b] + L.g[b] * (double)qt);     // float64 TD glue (DDPG.py:80-84)
+                L.y[b] = y;
+                dv.tap_y[(size_t)agent * RLC_MAX_BATCH + b] = y;
+            }
+            __syncthreads();
+            STAMP();
+        } else {
+            STAMP();
+            STAMP();      // (diagnostic build: the stamp indices of the later phases stay what they were)
         }
-        __syncthreads();
-        STAMP();
 
         // ================= step 3: critic step =================
         u.trunk(th + d.oWc1, th + d.obc1, L.x);           // the critic's first layer (= the shared trunk in the hydra network)
@@ -274,6 +289,12 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         __syncthreads();
         STAMP();
         for (int b = tid; b < B; b += kThreads) {
+            if constexpr (td_in_dq) {
+                const float qt = u.template part_sum<1>(L.partq, b, 0) + tt[d.obc3];
+                const float y = (float)(L.r[b] + L.g[b] * (double)qt);     // float64 TD glue (DDPG.py:80-84)
+                L.y[b] = y;
+                dv.tap_y[(size_t)agent * RLC_MAX_BATCH + b] = y;
+            }
             const float q = u.template part_sum<1>(L.part, b, 0) + th[d.obc3];
             L.q[b] = q;
             dv.tap_q[(size_t)agent * RLC_MAX_BATCH + b] = q;
@@ -370,7 +391,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         __syncthreads();
         STAMP();
         f32x4 acc7[MT][NTW];          // the critic's hidden contraction at the new trunk (its action rows enter in the epilogue)
-        if constexpr (fuse_fwd) u.fwd_gemm2(acc, acc7, th + d.oWa2, th + d.oWc2, HA, H1);
+        if constexpr (fuse_fwd) u.template fwd_gemm2<!WIDE>(acc, acc7, th + d.oWa2, th + d.oWc2, HA, H1);
         else u.fwd_gemm(acc, th + d.oWa2, HA, H1);
         u.template bias_relu<0>(acc, th + d.oba2, HA);
         u.template row_dot<false, AD>(acc, HA, [&](int n, int j) { return th[d.oWa3 + n * AD + j]; }, L.part);   // z partials
@@ -462,6 +483,9 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
         if constexpr (WIDE) __syncthreads();      // the masks stored above
         u.template bwd_gemm<AD, -2>(acc, th + d.oWa2, HA, H1, L.dz, L.wvec);
         __syncthreads();
+        // every wave has computed alpha_a: the actor's beta powers step here, not behind a barrier pair of their own at
+        // the end of the update (their next reader is the next update's alpha_a, a dozen barriers on)
+        if (tid == 0) { pw[0] *= 0.9f; pw[1] *= 0.999f; }
         if (sep) {
             u.trunk(th + d.oW1, th + d.ob1, L.x);             // the actor's image again: its relu mask and the weight-gradient operand
             __syncthreads();
@@ -529,10 +553,8 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
                 }
             }
         }
-        __syncthreads();
+        __syncthreads();      // the one barrier between updates (the actor's beta powers were stepped behind the backward GEMM)
         STAMP();
-        if (tid == 0) { pw[0] *= 0.9f; pw[1] *= 0.999f; }
-        __syncthreads();
     }
 #ifdef RLC_STAMPS
     if (tid == 0 && stamp_buf) {

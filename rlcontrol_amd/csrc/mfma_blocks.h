@@ -572,8 +572,13 @@ struct Blk {
     // the MFMAs, one loop prologue / drain and one barrier fall away, and neither accumulator set has to be parked in
     // registers across the other GEMM's loop (where the compiler spilled it: NAF 224 VGPRs = 0.6 MB of scratch traffic
     // per update).  Same structure and pinning as fwd_loop; summation order per output element unchanged.
+    //
+    // PACK (the split 13th tile with at most 8 real columns, widths 193..200): both matrices' ragged tiles are half
+    // padding, so the share runs as ONE 16-column tile -- lanes c < 8 stream WA's block column c, lanes c >= 8 WB's
+    // block column c - 8 (a per-lane base pointer, chosen once) -- into accxA alone; accxB is not touched.  Each
+    // accumulator lane still sees its own column's k-ordered chain; fwd_gemm2 sorts the columns out afterwards.
     // ---------------------------------------------------------------------------------------
-    template <int NOWN, int XMODE>
+    template <int NOWN, int XMODE, bool PACK = false>
     __device__ __forceinline__ void fwd_loop2(f32x4 (&accA)[MT][NTW], f32x4 (&accB)[MT][NTW], const float* WA, const float* WB,
                                               int NT, int KB, bool tail8, f32x4 (&accxA)[MXS], f32x4 (&accxB)[MXS], int xt,
                                               int xm0) {
@@ -593,8 +598,10 @@ struct Blk {
         f32x4 tqA[NOWN], tqB[NOWN];                                        // T4: the tail tile's 4x4x1 accumulators
 #pragma unroll
         for (int i = 0; i < NOWN; i++) { tqA[i] = f32x4{0.f, 0.f, 0.f, 0.f}; tqB[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        const size_t tx = ((size_t)xt << 8) + lofs;
-        const float* wpxA = WA + tx;
+        // PACK: the lane's matrix and its column inside the packed tile (c & 7); otherwise column c of both matrices
+        const int cx = PACK ? (c & 7) : c;
+        const size_t tx = ((size_t)xt << 8) + (PACK ? ((((cx >> 2) << 4) + 4 * g) << 2) + (cx & 3) : lofs);
+        const float* wpxA = ((PACK && c >= 8) ? WB : WA) + tx;
         const float* wpxB = WB + tx;
         const lds_f32* apx = ap + 16 * xm0 * LDH;
         auto xrow = [&](int m) { return XMODE == 2 ? apt : apx + 16 * (xm0 + m < MT ? m : 0) * LDH; };
@@ -607,7 +614,7 @@ struct Blk {
 #pragma unroll
                 for (int s2 = 0; s2 < 4; s2++) {
                     db[0][s2] = wpxA[(size_t)ch * wstep + 4 * s2];
-                    db[1][s2] = wpxB[(size_t)ch * wstep + 4 * s2];
+                    if constexpr (!PACK) db[1][s2] = wpxB[(size_t)ch * wstep + 4 * s2];
                 }
             }
         };
@@ -619,10 +626,10 @@ struct Blk {
                     for (int m = 0; m < NX; m++) {
                         if (XMODE == 2) {
                             accxA[m] = mfma4(da[m][s2], db[0][s2], accxA[m]);
-                            accxB[m] = mfma4(da[m][s2], db[1][s2], accxB[m]);
+                            if constexpr (!PACK) accxB[m] = mfma4(da[m][s2], db[1][s2], accxB[m]);
                         } else {
                             accxA[m] = mfma16(da[m][s2], db[0][s2], accxA[m]);
-                            accxB[m] = mfma16(da[m][s2], db[1][s2], accxB[m]);
+                            if constexpr (!PACK) accxB[m] = mfma16(da[m][s2], db[1][s2], accxB[m]);
                         }
                     }
             }
@@ -661,7 +668,8 @@ struct Blk {
         loadX(ax0, bx0, 0);
         int ch = 0;
         auto pin = [&]() {
-            __builtin_amdgcn_sched_group_barrier(0x020, 8 * NOWN + (XTRA ? 8 : 0), 0);      // VMEM read
+            constexpr int XB = PACK ? 4 : 8;           // the split share's weight loads, and MFMAs per A fragment
+            __builtin_amdgcn_sched_group_barrier(0x020, 8 * NOWN + (XTRA ? XB : 0), 0);     // VMEM read
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // DS read
@@ -669,7 +677,7 @@ struct Blk {
             }
             if (XTRA) {
                 __builtin_amdgcn_sched_group_barrier(0x100, NX, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 8 * NX, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, XB * NX, 0);
             }
         };
         for (; ch + 2 <= KB; ch += 2) {
@@ -719,18 +727,19 @@ struct Blk {
                         }
                     }
             if (XTRA) {
-                const size_t txb = ((size_t)xt << 8) + (size_t)KB * wstep + tofs;
+                const size_t txb = ((size_t)xt << 8) + (size_t)KB * wstep + (PACK ? ((((cx >> 2) << 4) + 2 * g) << 2) + (cx & 3) : tofs);
+                const float* WXA = (PACK && c >= 8) ? WB : WA;
 #pragma unroll
                 for (int m = 0; m < NX; m++) {
                     const f32x2 avx = *reinterpret_cast<const RLC_LDS f32x2*>(xrow(m) + kofs);
 #pragma unroll
                     for (int s2 = 0; s2 < 2; s2++) {
                         if (XMODE == 2) {
-                            accxA[m] = mfma4(avx[s2], WA[txb + 4 * s2], accxA[m]);
-                            accxB[m] = mfma4(avx[s2], WB[txb + 4 * s2], accxB[m]);
+                            accxA[m] = mfma4(avx[s2], WXA[txb + 4 * s2], accxA[m]);
+                            if constexpr (!PACK) accxB[m] = mfma4(avx[s2], WB[txb + 4 * s2], accxB[m]);
                         } else {
-                            accxA[m] = mfma16(avx[s2], WA[txb + 4 * s2], accxA[m]);
-                            accxB[m] = mfma16(avx[s2], WB[txb + 4 * s2], accxB[m]);
+                            accxA[m] = mfma16(avx[s2], WXA[txb + 4 * s2], accxA[m]);
+                            if constexpr (!PACK) accxB[m] = mfma16(avx[s2], WB[txb + 4 * s2], accxB[m]);
                         }
                     }
                 }
@@ -742,10 +751,18 @@ struct Blk {
                 accA[MT - 1][i] += tail_finish(tqA[i]);
                 accB[MT - 1][i] += tail_finish(tqB[i]);
             }
-            if constexpr (XMODE == 2) { accxA[0] = tail_finish(accxA[0]); accxB[0] = tail_finish(accxB[0]); }
+            if constexpr (XMODE == 2) {
+                accxA[0] = tail_finish(accxA[0]);
+                if constexpr (!PACK) accxB[0] = tail_finish(accxB[0]);
+            }
         }
     }
 
+    // PACK: where the split 13th tile has at most 8 real columns (N mod 16 in 1..8) it runs packed (fwd_loop2); the other
+    // widths take the unpacked loops.  The hand-off carries the packed tile once; wave 4, its owner, then moves WB's columns
+    // from lanes c >= 8 to lanes c - 8 (one DPP row rotation per register) and zeroes what a padded column holds, so
+    // every epilogue sees the accumulators of the unpacked path, bit for bit.
+    template <bool PACK = false>
     __device__ __forceinline__ void fwd_gemm2(f32x4 (&accA)[MT][NTW], f32x4 (&accB)[MT][NTW], const float* WA, const float* WB,
                                               int N, int K) {
         const int NT = (N + 15) >> 4;
@@ -759,7 +776,28 @@ struct Blk {
         const int KB = tail8 ? K >> 4 : (K + 15) >> 4;
         f32x4 accxA[MXS], accxB[MXS];
         if constexpr (NTW >= 2) {
-            if (split_mode(NT)) {
+            bool packed = false;                 // workgroup-uniform
+            if constexpr (PACK) packed = split_mode(NT) && ((N - 1) & 15) < 8;
+            if (packed) {
+#pragma unroll
+                for (int m = 0; m < MXS; m++) accxA[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (T4 && wave == 7) fwd_loop2<1, T4 ? 2 : 1, PACK>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(3));
+                else if (wave >= 4) fwd_loop2<1, 1, PACK>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(wave - 4));
+                else fwd_loop2<2, 0>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, 0, 0);
+                collect_split<false>(accA, accxA);
+                if (wave == 4) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const float v = accA[mt][1][r];
+                            // row_ror:8 -- lane c of a 16-lane row reads lane c ^ 8
+                            const float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
+                            accA[mt][1][r] = c < 8 ? v : 0.0f;
+                            accB[mt][1][r] = c < 8 ? o : 0.0f;
+                        }
+                }
+            } else if (split_mode(NT)) {
 #pragma unroll
                 for (int m = 0; m < MXS; m++) { accxA[m] = f32x4{0.f, 0.f, 0.f, 0.f}; accxB[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
                 if (T4 && wave == 7) fwd_loop2<1, T4 ? 2 : 1>(accA, accB, WA, WB, NT, KB, tail8, accxA, accxB, NT - 1, share_lo(3));
