@@ -434,6 +434,61 @@ int rlc_optq_qval(rlc_optq* h, int32_t agent, int32_t n, const double* states, c
 int rlc_optq_set_kernel(rlc_optq* h, int32_t variant);
 int rlc_optq_get_kernel(const rlc_optq* h, int32_t* variant_in_use);
 
+
+/* ===================================== WireFitting =================================================
+ * The wire-fitting Q-learner (agents/WireFitting.py:11-83, agents/network/wf_network.py:8-171;
+ * jsonfiles/agent/wirefitting.json): one network puts out N = app_points wires, each an action ahat_i and a value
+ * qhat_i; Q(s,a) interpolates the wire values with weights 1 / (|a - ahat_i|^2 + c_i (max_j qhat_j - qhat_i) + 1e-5),
+ * c = sigmoid(smooth_c) (wf_network.py:106-125).  The greedy action is the wire of the largest value, the lowest index
+ * among equal maxima (tf.argmax, :97); the TD target takes the target network's largest wire value (:94,153-159).
+ * Parameter blob, variable creation order (wf_network.py:76-92,116):
+ *   W1[S][L1] b1 | W2[L1][L2] b2 | Wa[L2][N*A] ba | Wq[L2][N] bq | smooth_c[N],   wire i = columns i*A .. i*A+A-1 of Wa.
+ * blob selector: 0 theta, 1 target, 2 Adam m, 3 Adam v. */
+typedef rlc_handle rlc_wf;
+typedef struct rlc_wf_config {
+    int32_t device, n_agents, state_dim, action_dim;   /* action_dim <= 6 */
+    int32_t l1_dim, l2_dim;                             /* jsonfiles/agent/wirefitting.json */
+    int32_t batch_size, clip_state;                     /* clip_state: norm_type != 'none' (wf_network.py:73-74) */
+    int64_t buffer_size;
+    float tau;
+    int32_t norm_type;           /* RLC_NORM_NONE ('none' / 'input_norm') only: 'layer' and 'batch' are refused */
+    const float* state_min;      /* [state_dim] */
+    const float* state_max;
+    const float* learning_rate;  /* [n_agents] (wf_network.py:10,50) */
+    const uint64_t* seed;        /* [n_agents] Philox keys of the device sampler */
+    int32_t app_points;          /* N >= 1, N * action_dim <= 1024 (wf_network.py:20) */
+    float action_max0;           /* action_max[0]: the ONE scalar that scales every dimension of every wire action (:88) */
+} rlc_wf_config;
+
+int rlc_wf_create(const rlc_wf_config* cfg, rlc_wf** out);                /* wf_network.py:9-58 */
+int rlc_wf_param_count(const rlc_wf* h, int64_t* out_p);
+int rlc_wf_set_blob(rlc_wf* h, int32_t agent, int32_t which, const float* src, int64_t n);
+int rlc_wf_get_blob(rlc_wf* h, int32_t agent, int32_t which, float* dst, int64_t n);
+int rlc_wf_set_beta_powers(rlc_wf* h, int32_t agent, const float* pw2);   /* {beta1^t, beta2^t} of the one Adam (:50) */
+int rlc_wf_get_beta_powers(rlc_wf* h, int32_t agent, float* pw2);
+int rlc_wf_init_target(rlc_wf* h, int32_t agent);                         /* wf_network.py:53,161-162 */
+/* predict_action (wf_network.py:136-143, agents/WireFitting.py:25): out_action [n][A] = the arg-max wire's action;
+ * out_wires (may be NULL) = every wire's action [n][N][A] followed by every wire's value [n][N] */
+int rlc_wf_act(rlc_wf* h, int32_t first_agent, int32_t n, const double* states, float* out_action, float* out_wires);
+/* queued / fetched as rlc_ddpg_act_queue / rlc_ddpg_act_fetch (the host adds the exploration noise after the fetch) */
+int rlc_wf_act_queue(rlc_wf* h, int32_t first_agent, int32_t n, const double* states);
+int rlc_wf_act_fetch(rlc_wf* h, int32_t first_agent, int32_t n, float* out_action, float* out_wires);
+/* BaseAgent.learn for every agent: sample_batch + WireFitting_Network_Manager.update_network
+ * (agents/WireFitting.py:66-77; wf_network.py:127-134,153-165) */
+int rlc_wf_update(rlc_wf* h, int32_t n_updates, const int64_t* host_indices);
+int rlc_wf_update_batch(rlc_wf* h, int32_t agent, int32_t batch, const double* states, const double* actions,
+                        const double* next_states, const double* rewards, const double* gammas);
+/* taps of the last update: 0 Q(s,a), 1 TD target y, 2 max_i qhat'_i(s') (n = batch); 3 gradient blob (n = P) */
+int rlc_wf_last_tap(rlc_wf* h, int32_t agent, int32_t which, float* dst, int64_t n);
+int rlc_wf_enable_grad_taps(rlc_wf* h, int32_t on);
+/* Q(s,a) rows on one agent's online network (getQFunction, wf_network.py:167-171) */
+int rlc_wf_qval(rlc_wf* h, int32_t agent, int32_t n, const double* states, const double* actions, float* out_q);
+/* 0 auto and 1 generic both mean the any-shape kernel; 2 is refused: "WireFitting runs on the any-shape kernel only" */
+int rlc_wf_set_kernel(rlc_wf* h, int32_t variant);
+int rlc_wf_get_kernel(const rlc_wf* h, int32_t* variant_in_use);
+/* 1 is accepted; anything above is refused: "WireFitting has no latency mode" */
+int rlc_wf_set_split(rlc_wf* h, int32_t n_workgroups);
+
 /* ---------------------------------------------------------------------------------------------------
  * On-device experiment loop: Experiment.run of the reference
  * (experiment.py:52-217) for every agent of a DDPG population, with the environment simulated on the GPU.

@@ -37,6 +37,9 @@ EXPORTS = (
     "rlc_optq_create", "rlc_optq_param_count", "rlc_optq_set_blob", "rlc_optq_get_blob", "rlc_optq_get_beta_powers",
     "rlc_optq_init_target", "rlc_optq_act", "rlc_optq_act_queue", "rlc_optq_act_fetch", "rlc_optq_update", "rlc_optq_update_batch",
     "rlc_optq_last_tap", "rlc_optq_enable_grad_taps", "rlc_optq_qval", "rlc_optq_set_kernel", "rlc_optq_get_kernel",
+    "rlc_wf_create", "rlc_wf_param_count", "rlc_wf_set_blob", "rlc_wf_get_blob", "rlc_wf_set_beta_powers", "rlc_wf_get_beta_powers",
+    "rlc_wf_init_target", "rlc_wf_act", "rlc_wf_act_queue", "rlc_wf_act_fetch", "rlc_wf_update", "rlc_wf_update_batch",
+    "rlc_wf_last_tap", "rlc_wf_enable_grad_taps", "rlc_wf_qval", "rlc_wf_set_kernel", "rlc_wf_get_kernel", "rlc_wf_set_split",
     "rlc_ddpg_rollout_create", "rlc_ddpg_rollout_run", "rlc_sac_rollout_create", "rlc_sac_rollout_run", "rlc_kl_rollout_create", "rlc_kl_rollout_run",
     "rlc_naf_rollout_create", "rlc_naf_rollout_run", "rlc_rollout_counts", "rlc_rollout_train_log",
     "rlc_rollout_eval_log", "rlc_rollout_observation",
@@ -117,6 +120,18 @@ class rlc_optq_config(ctypes.Structure):
         ("learning_rate", ctypes.POINTER(ctypes.c_float)), ("seed", ctypes.POINTER(ctypes.c_uint64)),
         ("n_nodes", ctypes.c_int32), ("reserved0", ctypes.c_int32),
         ("node_actions", ctypes.POINTER(ctypes.c_float)),
+    ]
+
+
+class rlc_wf_config(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("state_dim", ctypes.c_int32),
+        ("action_dim", ctypes.c_int32), ("l1_dim", ctypes.c_int32), ("l2_dim", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32), ("clip_state", ctypes.c_int32), ("buffer_size", ctypes.c_int64),
+        ("tau", ctypes.c_float), ("norm_type", ctypes.c_int32),
+        ("state_min", ctypes.POINTER(ctypes.c_float)), ("state_max", ctypes.POINTER(ctypes.c_float)),
+        ("learning_rate", ctypes.POINTER(ctypes.c_float)), ("seed", ctypes.POINTER(ctypes.c_uint64)),
+        ("app_points", ctypes.c_int32), ("action_max0", ctypes.c_float),
     ]
 
 

@@ -10,9 +10,10 @@
 #include "sac_common.h"
 #include "naf_common.h"
 #include "optq_common.h"
+#include "wf_common.h"
 
 // KL: ReverseKL / ForwardKL, on RlcSacDev
-enum RlcAlgo { RLC_ALGO_DDPG = 1, RLC_ALGO_SAC = 2, RLC_ALGO_NAF = 3, RLC_ALGO_KL = 4, RLC_ALGO_OPTQ = 5 };
+enum RlcAlgo { RLC_ALGO_DDPG = 1, RLC_ALGO_SAC = 2, RLC_ALGO_NAF = 3, RLC_ALGO_KL = 4, RLC_ALGO_OPTQ = 5, RLC_ALGO_WF = 6 };
 
 struct rlc_handle {
     int algo;
@@ -49,6 +50,8 @@ struct rlc_handle {
     RlcNafDev naf;
     // ---- OptimalQ
     RlcOptqDev optq;
+    // ---- WireFitting
+    RlcWfDev wf;
     // ---- on-device experiment loop (rlc_api_rollout.hip)
     bool has_env;
     RlcEnvDev env;
@@ -70,14 +73,15 @@ int rlc_h_split_after_launch(rlc_handle* h);
 // ---- what differs between the algorithms on the host side is data: the tables below; the bodies are in rlc_api.hip ----
 inline const char* rlc_algo_name(int algo) {
     return algo == RLC_ALGO_DDPG ? "DDPG" : algo == RLC_ALGO_SAC ? "SoftActorCritic" : algo == RLC_ALGO_NAF ? "NAF"
-           : algo == RLC_ALGO_OPTQ ? "OptimalQ" : "ReverseKL / ForwardKL";
+           : algo == RLC_ALGO_OPTQ ? "OptimalQ" : algo == RLC_ALGO_WF ? "WireFitting" : "ReverseKL / ForwardKL";
 }
 #define RLC_NEED(h, a) RLC_REQUIRE((h) && (h)->algo == (a), "handle is not a %s population", rlc_algo_name(a))
 
 // f(device view of the handle's algorithm)
 template <class F>
 int rlc_h_with_dev(rlc_handle* h, F f) {
-    return h->algo == RLC_ALGO_DDPG ? f(h->dv) : h->algo == RLC_ALGO_NAF ? f(h->naf) : h->algo == RLC_ALGO_OPTQ ? f(h->optq) : f(h->sac);
+    return h->algo == RLC_ALGO_DDPG ? f(h->dv) : h->algo == RLC_ALGO_NAF ? f(h->naf) : h->algo == RLC_ALGO_OPTQ ? f(h->optq)
+           : h->algo == RLC_ALGO_WF ? f(h->wf) : f(h->sac);
 }
 
 // the per-agent parameter-shaped blobs [n_agents][Ppad], in the order of the ABI's blob selector
@@ -85,11 +89,13 @@ inline std::vector<float**> rlc_blobs(RlcDev& v) { return {&v.theta, &v.theta_t,
 inline std::vector<float**> rlc_blobs(RlcSacDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
 inline std::vector<float**> rlc_blobs(RlcNafDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
 inline std::vector<float**> rlc_blobs(RlcOptqDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
+inline std::vector<float**> rlc_blobs(RlcWfDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
 // the gradient taps, blobs that exist only after *_enable_grad_taps
 inline std::vector<float**> rlc_grad_taps(RlcDev& v) { return {&v.tap_gc, &v.tap_ga}; }
 inline std::vector<float**> rlc_grad_taps(RlcSacDev& v) { return {&v.tap_g}; }
 inline std::vector<float**> rlc_grad_taps(RlcNafDev& v) { return {&v.tap_g}; }
 inline std::vector<float**> rlc_grad_taps(RlcOptqDev& v) { return {&v.tap_g}; }
+inline std::vector<float**> rlc_grad_taps(RlcWfDev& v) { return {&v.tap_g}; }
 // the same dims with the other weight layout
 inline RlcDims rlc_with_layout(const RlcDims& d, int blocked) {
     return rlc_make_dims(d.S, d.A, d.H1, d.HA, d.HC, d.B, blocked, d.norm, d.sep);
@@ -101,10 +107,12 @@ inline RlcNafDims rlc_with_layout(const RlcNafDims& d, int blocked) {
     return rlc_naf_make_dims(d.S, d.A, d.L1, d.L2, d.B, blocked, d.norm);
 }
 inline RlcOptqDims rlc_with_layout(const RlcOptqDims& d, int) { return d; }     // one layout: row-major
+inline RlcWfDims rlc_with_layout(const RlcWfDims& d, int) { return d; }         // one layout: row-major
 inline int rlc_beta_powers(const RlcDev&) { return 4; }
 inline int rlc_beta_powers(const RlcSacDev&) { return 4; }
 inline int rlc_beta_powers(const RlcNafDev&) { return 2; }
 inline int rlc_beta_powers(const RlcOptqDev&) { return 2; }
+inline int rlc_beta_powers(const RlcWfDev&) { return 2; }
 // tap `which` of the last update: all agents' array (null: not available), per-agent stride, floats the caller gets,
 // blob = stored in the padded device layout of a parameter blob
 struct RlcTap { const float* base; size_t stride; long long len; bool blob; };
@@ -141,6 +149,12 @@ inline RlcTap rlc_tap(const RlcOptqDev& v, int which, int B) {
                         {v.tap_astar, MB * A, B * (long long)A, false}, {v.tap_g, (size_t)v.d.Ppad, v.d.P, true}};
     return which >= 0 && which < 5 ? t[which] : RlcTap{nullptr, 0, 0, false};
 }
+inline RlcTap rlc_tap(const RlcWfDev& v, int which, int B) {
+    const size_t MB = RLC_MAX_BATCH;
+    const RlcTap t[] = {{v.tap_q, MB, B, false}, {v.tap_y, MB, B, false}, {v.tap_maxq, MB, B, false},
+                        {v.tap_g, (size_t)v.d.Ppad, v.d.P, true}};
+    return which >= 0 && which < 4 ? t[which] : RlcTap{nullptr, 0, 0, false};
+}
 // kernel variant in use (1 generic, 2 mfma): the request h->variant (0 auto) resolved against the shape support
 inline int rlc_h_variant(const rlc_handle* h) {
     if (h->variant == 1 || h->variant == 2) return h->variant;
@@ -149,6 +163,7 @@ inline int rlc_h_variant(const rlc_handle* h) {
         case RLC_ALGO_SAC: return rlc_sac_mfma_supported(h->sac.d) ? 2 : 1;
         case RLC_ALGO_NAF: return rlc_naf_mfma_supported(h->naf.d) ? 2 : 1;
         case RLC_ALGO_OPTQ: return 1;     // the any-shape kernel only
+        case RLC_ALGO_WF: return 1;       // the any-shape kernel only
         // above one action dimension the KL MFMA kernel is opt-in (rlc_kl_set_kernel)
         default: return (h->sac.d.A == 1 && rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes)) ? 2 : 1;
     }

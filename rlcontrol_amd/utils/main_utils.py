@@ -15,6 +15,7 @@ _AGENTS = {
     "ReverseKL": ("rlcontrol_amd.agents.ReverseKL", "ReverseKL"),
     "ForwardKL": ("rlcontrol_amd.agents.ForwardKL", "ForwardKL"),
     "OptimalQ": ("rlcontrol_amd.agents.OptimalQ", "OptimalQ"),
+    "WireFitting": ("rlcontrol_amd.agents.WireFitting", "WireFitting"),
 }
 
 
