@@ -489,6 +489,77 @@ int rlc_wf_get_kernel(const rlc_wf* h, int32_t* variant_in_use);
 /* 1 is accepted; anything above is refused: "WireFitting has no latency mode" */
 int rlc_wf_set_split(rlc_wf* h, int32_t n_workgroups);
 
+
+/* ===================================== ActorExpert =================================================
+ * The Actor-Expert agent (agents/ActorExpert.py:13-192, agents/network/ae_network.py:7-507; jsonfiles/agent/ae.json):
+ * a hydra network with a shared first layer, a mixture-density actor of M = num_modal Gaussians (mean, sigma, alpha
+ * heads) and an expert Q(s,a) whose action rows enter at the second layer.  One update: Q-learning expert step with
+ * a' = the mean of the largest-alpha mode of the ONLINE actor on s' and the TARGET Q; n = num_samples actions per row
+ * from the mixture, the top_k of them by Q, one actor step on their clipped negative log-density; Polyak on everything.
+ * Parameter blob, variable creation order (ae_network.py:138-229):
+ *   W1[S][L1] b1 | Wa2[L1][La] ba2 | Wm[La][M*A] bm | Ws[La][M*A] bs | Wal[La][M] bal | Wq2[L1+A][Le] bq2 | Wq3[Le] bq3,
+ * mode m, dimension d = column m*A + d of Wm and Ws; the action rows are last in Wq2.
+ * blob selector: 0 theta, 1 target, 2 / 3 the actor Adam's m / v, 4 / 5 the expert Adam's m / v (both own W1, b1).
+ * Random draws: the caller's (u uniform in [0,1), eps N(0,1)), or both NULL for the device's Philox stream keyed by the
+ * agent's seed.  Mode of a draw: the number of cdf entries <= u, cdf = cumsum(alpha) / its last element
+ * (numpy's RandomState.choice); action = clip(mean[mode] + sigma[mode] * eps, action_min, action_max). */
+typedef rlc_handle rlc_ae;
+typedef struct rlc_ae_config {
+    int32_t device, n_agents, state_dim, action_dim;    /* action_dim <= 6 */
+    int32_t shared_l1_dim, actor_l2_dim, expert_l2_dim; /* jsonfiles/agent/ae.json */
+    int32_t num_modal;                                   /* 1 .. 8 */
+    int32_t num_samples;                                 /* 1 .. 1024 */
+    int32_t top_k;                                       /* int(num_samples * rho), formed by the caller; 1 .. num_samples */
+    int32_t batch_size, clip_state;                      /* clip_state: norm_type != 'none' (ae_network.py:130-131) */
+    int64_t buffer_size;
+    float tau;
+    int32_t norm_type;           /* RLC_NORM_NONE ('none' / 'input_norm') only: 'layer' and 'batch' are refused */
+    const float* state_min;      /* [state_dim] */
+    const float* state_max;
+    const float* action_min;     /* [action_dim]: the clip of a sampled action */
+    const float* action_max;     /* [action_dim]: the clip, and the scale of the mean head per dimension */
+    const float* actor_lr;       /* [n_agents] */
+    const float* expert_lr;      /* [n_agents] */
+    const uint64_t* seed;        /* [n_agents] Philox keys: the device sampler and the device's draws */
+} rlc_ae_config;
+
+int rlc_ae_create(const rlc_ae_config* cfg, rlc_ae** out);
+int rlc_ae_param_count(const rlc_ae* h, int64_t* out_p);
+int rlc_ae_set_blob(rlc_ae* h, int32_t agent, int32_t which, const float* src, int64_t n);
+int rlc_ae_get_blob(rlc_ae* h, int32_t agent, int32_t which, float* dst, int64_t n);
+/* {actor beta1^t, actor beta2^t, expert beta1^t, expert beta2^t} */
+int rlc_ae_set_beta_powers(rlc_ae* h, int32_t agent, const float* pw4);
+int rlc_ae_get_beta_powers(rlc_ae* h, int32_t agent, float* pw4);
+int rlc_ae_init_target(rlc_ae* h, int32_t agent);
+/* sample 0: predict_action (ae_network.py:409-435), the mean of the largest-alpha mode; sample 1: one draw of
+ * sample_action (:461-496) clipped to the action bounds, from u [n] and eps [n][A] or (both NULL) the device's stream */
+int rlc_ae_act(rlc_ae* h, int32_t first_agent, int32_t n, const double* states, int32_t sample, const float* u,
+               const float* eps, float* out_actions);
+/* queued / fetched as rlc_ddpg_act_queue / rlc_ddpg_act_fetch */
+int rlc_ae_act_queue(rlc_ae* h, int32_t first_agent, int32_t n, const double* states, int32_t sample, const float* u,
+                     const float* eps);
+int rlc_ae_act_fetch(rlc_ae* h, int32_t first_agent, int32_t n, float* out_actions);
+/* BaseAgent.learn for every agent: sample_batch + ActorExpert_Network_Manager.update_network (ActorExpert.py:116-185).
+ * u [n_agents][n_updates][batch][num_samples], eps [..][num_samples][action_dim], or both NULL */
+int rlc_ae_update(rlc_ae* h, int32_t n_updates, const int64_t* host_indices, const float* u, const float* eps);
+/* u [batch][num_samples], eps [batch][num_samples][action_dim], or both NULL */
+int rlc_ae_update_batch(rlc_ae* h, int32_t agent, int32_t batch, const double* states, const double* actions,
+                        const double* next_states, const double* rewards, const double* gammas, const float* u,
+                        const float* eps);
+/* taps of the last update: 0 Q(s,a), 1 TD target y (n = batch); 2 a' (n = batch * action_dim); 3 the sampled actions
+ * (n = batch * num_samples * action_dim); 4 their Q (n = batch * num_samples); 5 the selected sample indices of every
+ * row in ascending order, as floats (n = batch * top_k); 6 the actor loss (n = 1); 7 the actor's gradient blob, 8 the
+ * expert's (n = P each; elements the optimizer does not own are zero) */
+int rlc_ae_last_tap(rlc_ae* h, int32_t agent, int32_t which, float* dst, int64_t n);
+int rlc_ae_enable_grad_taps(rlc_ae* h, int32_t on);
+/* Q(s,a) rows on one agent's online network (getQFunction, ae_network.py:504-507) */
+int rlc_ae_qval(rlc_ae* h, int32_t agent, int32_t n, const double* states, const double* actions, float* out_q);
+/* 0 auto and 1 generic both mean the any-shape kernel; 2 is refused: "ActorExpert runs on the any-shape kernel only" */
+int rlc_ae_set_kernel(rlc_ae* h, int32_t variant);
+int rlc_ae_get_kernel(const rlc_ae* h, int32_t* variant_in_use);
+/* 1 is accepted; anything above is refused: "ActorExpert has no latency mode" */
+int rlc_ae_set_split(rlc_ae* h, int32_t n_workgroups);
+
 /* ---------------------------------------------------------------------------------------------------
  * On-device experiment loop: Experiment.run of the reference
  * (experiment.py:52-217) for every agent of a DDPG population, with the environment simulated on the GPU.

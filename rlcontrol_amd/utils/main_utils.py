@@ -16,6 +16,7 @@ _AGENTS = {
     "ForwardKL": ("rlcontrol_amd.agents.ForwardKL", "ForwardKL"),
     "OptimalQ": ("rlcontrol_amd.agents.OptimalQ", "OptimalQ"),
     "WireFitting": ("rlcontrol_amd.agents.WireFitting", "WireFitting"),
+    "ActorExpert": ("rlcontrol_amd.agents.ActorExpert", "ActorExpert"),
 }
 
 
