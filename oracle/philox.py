@@ -48,15 +48,16 @@ def below(p, n):
     return (u * n) >> 64
 
 
-def sample_distinct(n, k, key, call):
-    """k distinct logical indices in range(n) (rlc_sample_distinct): both regimes."""
+def sample_distinct_rounds(n, k, key, call):
+    """(indices, redraw rounds) of rlc_sample_distinct: both regimes.  A redraw round is one pass of the sparse regime
+    after the first, taken because some candidate repeated a lower-numbered one; the dense regime never redraws."""
     if 3 * k >= n:
         pool = list(range(n))
         for i in range(k):
             p = philox4x32_10(key, call, 0x100000000 + i)
             j = i + below(p, n - i)
             pool[i], pool[j] = pool[j], pool[i]
-        return np.array(pool[:k], dtype=np.int64)
+        return np.array(pool[:k], dtype=np.int64), 0
     out = [-1] * k
     need = [True] * k
     rnd = 0
@@ -66,8 +67,13 @@ def sample_distinct(n, k, key, call):
                 out[t] = below(philox4x32_10(key, call, (rnd << 32) | t), n)
         need = [any(out[j] == out[t] for j in range(t)) for t in range(k)]
         if not any(need):
-            return np.array(out, dtype=np.int64)
+            return np.array(out, dtype=np.int64), rnd
         rnd += 1
+
+
+def sample_distinct(n, k, key, call):
+    """k distinct logical indices in range(n) (rlc_sample_distinct): both regimes."""
+    return sample_distinct_rounds(n, k, key, call)[0]
 
 
 def normal2(p):

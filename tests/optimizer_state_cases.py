@@ -12,6 +12,11 @@ def _bounds(S, A):
     return -np.ones(S) * 2, np.ones(S) * 2, np.linspace(1.0, 2.0, A)
 
 
+def _seeds(seeds, first, n_agents):
+    """a pop()'s per-agent Philox keys: the caller's, or the family's usual run first, first + 1, ..."""
+    return list(seeds) if seeds is not None else list(range(first, first + n_agents))
+
+
 class Case(object):
     """kernel: 'generic' or 'mfma' (the wide forms are opt-in through the same name); split: latency mode's workgroups"""
     SLOTS = {"adam": ("adam_m", "adam_v")}
@@ -106,13 +111,13 @@ class DDPGCase(Case):
         lay, P = self._vd().layout()
         return C.ddpg_spec(lay, P, lr[0], lr[1], TAU, separate=bool(self.kw.get("sep")))
 
-    def pop(self, n_agents=1, lr=None, cap=512):
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
         from rlcontrol_amd.hip_ddpg import DDPGPopulation
         lr = lr or self.LR
         smin, smax, amax = _bounds(self.S, self.A)
         S, A, H1, HA, HC = self.dims
         pop = DDPGPopulation(n_agents, S, A, H1, HA, HC, self.B, cap, TAU, smin, smax, -amax, amax, lr[0], lr[1],
-                             seeds=list(range(10, 10 + n_agents)), norm_type="layer" if self.kw.get("norm") else "input_norm",
+                             seeds=_seeds(seeds, 10, n_agents), norm_type="layer" if self.kw.get("norm") else "input_norm",
                              separate_networks=bool(self.kw.get("sep")))
         return self.select_kernel(pop)
 
@@ -151,13 +156,13 @@ class SACCase(Case):
         lay, P = layout(self.dims, bool(self.kw.get("norm")))
         return C.sac_spec(lay, P, lr[0], lr[1], TAU)
 
-    def pop(self, n_agents=1, lr=None, cap=512):
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
         from rlcontrol_amd.hip_sac import SACPopulation
         lr = lr or self.LR
         al, tau, smin0, smax0, amax0 = self.HYPER
         S, A, L1A, L2A, L1C, L2C = self.dims
         pop = SACPopulation(n_agents, S, A, L1A, L2A, L1C, L2C, self.B, cap, tau, smin0, smax0, amax0, lr[0], lr[1], al,
-                            seeds=list(range(5, 5 + n_agents)), norm_type="layer" if self.kw.get("norm") else "input_norm")
+                            seeds=_seeds(seeds, 5, n_agents), norm_type="layer" if self.kw.get("norm") else "input_norm")
         return self.select_kernel(pop)
 
 
@@ -190,12 +195,12 @@ class NAFCase(Case):
         lay, P = layout(self.dims, bool(self.kw.get("norm")))
         return C.naf_spec(lay, P, lr[0], TAU)
 
-    def pop(self, n_agents=1, lr=None, cap=512):
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
         from rlcontrol_amd.hip_naf import NAFPopulation
         lr = lr or self.LR
         smin, smax, amax = _bounds(self.S, self.A)
         pop = NAFPopulation(n_agents, *self.dims, self.B, cap, TAU, smin, smax, amax, lr[0],
-                            seeds=list(range(3, 3 + n_agents)), norm_type="layer" if self.kw.get("norm") else "input_norm")
+                            seeds=_seeds(seeds, 3, n_agents), norm_type="layer" if self.kw.get("norm") else "input_norm")
         return self.select_kernel(pop)
 
 
@@ -229,12 +234,12 @@ class KLCase(Case):
         lay, P = K.KlDims(*self.dims).layout()
         return C.kl_spec(lay, P, lr[0], lr[1], TAU, action_dim=self.A)
 
-    def pop(self, n_agents=1, lr=None, cap=512):
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
         from rlcontrol_amd.hip_kl import KLPopulation
         lr = lr or self.LR
         S, A, L1A, L2A, L1C, L2C = self.dims
         pop = KLPopulation(self.kw["kind"], n_agents, S, A, L1A, L2A, L1C, L2C, self.B, cap, TAU, self.AMAX0, lr[0], lr[1],
-                           self.ALPHA, seeds=list(range(5, 5 + n_agents)), n_param=self.kw.get("n_param", 64),
+                           self.ALPHA, seeds=_seeds(seeds, 5, n_agents), n_param=self.kw.get("n_param", 64),
                            l_param=self.kw.get("l_param"), action_max=np.full(A, self.AMAX0) if A > 1 else None)
         return self.select_kernel(pop)
 

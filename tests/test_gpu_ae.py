@@ -133,8 +133,8 @@ class AECase(Case):
                 C.Opt("actor", "actor", [(0, q0)], ALR, (0, 1), "grads_a")]
         return C.Spec(lay, P, opts, [(0, P)], TAU, "tf", lambda name, n: tol_g[name])
 
-    def pop(self):
-        return self.select_kernel(_pop(self.dims, self.B))
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
+        return self.select_kernel(_pop(self.dims, self.B, n_agents, lr or (ALR, ELR), cap, seeds))
 
 
 @pytest.mark.parametrize("case", [AECase(*W.SHAPES[4]), AECase(*W.SHAPES[1])], ids=lambda c: c.id)

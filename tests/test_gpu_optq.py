@@ -39,10 +39,11 @@ def _theta(dims, seed):
     return th
 
 
-def _pop(dims, B, grid, n_agents=1, lr=LR, cap=512, **kw):
+def _pop(dims, B, grid, n_agents=1, lr=LR, cap=512, seeds=None, **kw):
     from rlcontrol_amd.hip_optq import OptQPopulation
     smin, smax = _bounds(dims[0])
-    return OptQPopulation(n_agents, *dims, B, cap, TAU, smin, smax, lr, seeds=list(range(7, 7 + n_agents)),
+    return OptQPopulation(n_agents, *dims, B, cap, TAU, smin, smax, lr,
+                          seeds=seeds if seeds is not None else list(range(7, 7 + n_agents)),
                           node_actions=grid, **kw)
 
 
@@ -159,8 +160,8 @@ class OptQCase(Case):
         lay, P = R.layout(self.dims)
         return C.naf_spec(lay, P, (lr or (LR,))[0], TAU, tol_g=5e-5)          # one Adam and the average over every tensor
 
-    def pop(self, n_agents=1, lr=None, cap=512):
-        return self.select_kernel(_pop(self.dims, self.B, self.grid, n_agents, (lr or (LR,))[0], cap))
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
+        return self.select_kernel(_pop(self.dims, self.B, self.grid, n_agents, (lr or (LR,))[0], cap, seeds))
 
 
 @pytest.mark.parametrize("case", [OptQCase((3, 1, 200, 200), 32, (-2.0, 2.0), 1e-3), OptQCase((3, 1, 64, 72), 100, (-1.0, 1.0), 0.01)],

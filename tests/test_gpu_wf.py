@@ -34,10 +34,11 @@ def _rel(x, y):
     return float(np.max(np.abs(x - y)) / (np.max(np.abs(y)) + 1e-30))
 
 
-def _pop(dims, B, n_agents=1, lr=LR, cap=512, **kw):
+def _pop(dims, B, n_agents=1, lr=LR, cap=512, seeds=None, **kw):
     from rlcontrol_amd.hip_wf import WFPopulation
     smin, smax = W.bounds(dims[0])
-    return WFPopulation(n_agents, *dims, B, cap, TAU, smin, smax, AMAX0, lr, seeds=list(range(7, 7 + n_agents)), **kw)
+    return WFPopulation(n_agents, *dims, B, cap, TAU, smin, smax, AMAX0, lr,
+                        seeds=seeds if seeds is not None else list(range(7, 7 + n_agents)), **kw)
 
 
 def _held(label, dev, ref32, twin, bar):
@@ -126,8 +127,8 @@ class WFCase(Case):
         s = C.naf_spec(lay, P, (lr or (LR,))[0], TAU)                  # one Adam and the average over every tensor
         return s._replace(tol_g=lambda name, n: tol_g[name])
 
-    def pop(self, n_agents=1, lr=None, cap=512):
-        return self.select_kernel(_pop(self.dims, self.B, n_agents, (lr or (LR,))[0], cap))
+    def pop(self, n_agents=1, lr=None, cap=512, seeds=None):
+        return self.select_kernel(_pop(self.dims, self.B, n_agents, (lr or (LR,))[0], cap, seeds))
 
 
 @pytest.mark.parametrize("case", [WFCase((3, 1, 200, 200, 100), 32), WFCase((5, 2, 48, 64, 33), 32)], ids=lambda c: c.id)
