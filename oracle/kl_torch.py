@@ -167,16 +167,19 @@ def adam_171(param, grad, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
 
 class KLOracle(object):
     def __init__(self, kind, dims, theta, pi_lr, qv_lr, alpha, tau, amax0, n_param, optim_type="intg",
-                 q_update_type="non_sac", l_param=None, action_max=None):
+                 q_update_type="non_sac", l_param=None, action_max=None, dtype=torch.float32):
+        """dtype: float32 (the oracle the HIP kernels are held to) or float64 (the twin the fp32 run is held to): the
+        parameters, the minibatch and the quadrature rule are rounded to float32 first, as the device sees them, then widened"""
         assert kind in KINDS and optim_type in OPTIM_TYPES and q_update_type in Q_UPDATE_TYPES
         if kind == "forward" and optim_type != "intg":
             raise NotImplementedError("ForwardKL implements optim_type 'intg' only (forwardkl_network.py:153-158)")
         self.kind, self.d, self.optim_type, self.q_update_type = kind, dims, optim_type, q_update_type
         self.lay, P = dims.layout()
-        self.theta = torch.tensor(np.asarray(theta, np.float32).copy())
+        self.dt = dtype
+        self.theta = torch.tensor(np.asarray(theta, np.float32).copy()).to(dtype)
         self.theta_t = self.theta.clone()
-        self.m = torch.zeros(P)
-        self.v = torch.zeros(P)
+        self.m = torch.zeros(P, dtype=dtype)
+        self.v = torch.zeros(P, dtype=dtype)
         self.step = 0
         self.pi_lr, self.qv_lr, self.alpha, self.tau, self.amax0 = float(pi_lr), float(qv_lr), float(alpha), float(tau), float(amax0)
         if dims.t[1] == 1:
@@ -187,6 +190,7 @@ class KLOracle(object):
         else:
             na, nw = sparse_grid(l_param, dims.t[1], self.amax0 if action_max is None else action_max)
             self.nodes, self.weights = torch.tensor(na), torch.tensor(nw)
+        self.nodes, self.weights = self.nodes.to(dtype), self.weights.to(dtype)
         self.pi_end = self.lay["qW1"][0]
         self.q_end = self.lay["vW1"][0]
 
@@ -195,15 +199,16 @@ class KLOracle(object):
         S = self.d.t[0]
         with torch.no_grad():
             p = _views(self.theta, self.lay)
-            s = torch.tensor(np.asarray(states, np.float32).reshape(-1, S))
+            s = torch.tensor(np.asarray(states, np.float32).reshape(-1, S)).to(self.dt)
             mean, log_std = _pi(p, s)
-            z = mean if eps is None else mean + _sample_scale(log_std.exp()) * torch.tensor(np.asarray(eps, np.float32).reshape(mean.shape))
+            z = mean if eps is None else mean + _sample_scale(log_std.exp()) * \
+                torch.tensor(np.asarray(eps, np.float32).reshape(mean.shape)).to(self.dt)
             return (torch.tanh(z) * self.amax0).numpy()
 
     def update(self, s, a, s2, r, gam, eps, taps=False):
         S, A = self.d.t[0], self.d.t[1]
         B = len(np.reshape(r, -1))
-        f = lambda x, shp: torch.tensor(np.ascontiguousarray(x, np.float32).reshape(shp))
+        f = lambda x, shp: torch.tensor(np.ascontiguousarray(x, np.float32).reshape(shp)).to(self.dt)
         s, s2, a, eps = f(s, (B, S)), f(s2, (B, S)), f(a, (B, A)), f(eps, (B, A))
         r, gam = f(r, (B, 1)), f(gam, (B, 1))
         theta = self.theta.clone().requires_grad_(True)
