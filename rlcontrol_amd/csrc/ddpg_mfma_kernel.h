@@ -185,6 +185,7 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_mfma_kernel(RlcDev d
             if (!rlc_train_step_device(rollout, agent, (float*)L.hbuf, upd == 0 ? q8_first : 0)) continue;
         }
         // ================= sample + gather (utils/replaybuffer.py:32-37) =================
+        // (typed out: through rlc_pick_indices / rlc_locate_row of rlc_common.h the headline record lost 0.4 %)
         if (!(ablate(4) && upd > 0)) {
         u.sub_begin();
         const RlcRingMeta ring = dv.rep.ring[agent];

@@ -158,32 +158,18 @@ __global__ __launch_bounds__(kThreads) void rlc_ddpg_update_split_kernel(RlcDev 
         asm volatile("" : "+v"(u.c), "+v"(u.g), "+s"(u.wave));
         // ================= sample (every workgroup draws the whole index set) + gather of my rows =================
         const RlcRingMeta ring = dv.rep.ring[agent];
-        if (source == RLC_SRC_REPLAY_DEVICE_SAMPLER) {
-            __syncthreads();
-            rlc_sample_distinct(ring.size, Bfull, dv.rep.seed[agent], call0 + upd, L.pool, L.idx, L.dups);
-        } else if (source == RLC_SRC_REPLAY_HOST_INDICES) {
-            for (int b = tid; b < Bfull; b += kThreads)
-                L.idx[b] = host_idx[((size_t)rel * n_updates + upd) * Bfull + b];
-        }
-        __syncthreads();
+        // (call number call0 + upd, counter left alone: the launch stores call0 + n_updates once, at its end)
+        rlc_pick_indices<kThreads>(dv.rep, agent, ring, source, Bfull, host_idx, (size_t)rel * n_updates + upd, L.pool, L.idx,
+                                   L.dups, false, call0 + upd);
         for (int b = tid; b < B; b += kThreads) {
-            const int bg = row0 + b;
-            const float *ps, *pa, *ps2;
-            if (source == RLC_SRC_STAGING) {
-                const size_t slot = (size_t)agent * RLC_MAX_BATCH + bg;
-                ps = dv.rep.gs + slot * S; pa = dv.rep.ga + slot * AD; ps2 = dv.rep.gs2 + slot * S;
-                L.r[b] = dv.rep.gr[slot]; L.g[b] = dv.rep.gg[slot];
-            } else {
-                const size_t slot = (size_t)agent * dv.rep.cap + ring_slot(ring, dv.rep.cap, L.idx[bg]);
-                ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot * AD; ps2 = dv.rep.rs2 + slot * S;
-                L.r[b] = dv.rep.rr[slot]; L.g[b] = dv.rep.rg[slot];
-            }
+            const RlcRow w = rlc_locate_row(dv.rep, agent, ring, source, S, AD, row0 + b, L.idx);
+            L.r[b] = w.r; L.g[b] = w.g;
             for (int i = 0; i < S; i++) {
-                L.x[b * SMAX + i] = clip_state_val(ps[i], dv.clip_state, dv.smin[i], dv.smax[i]);
-                L.x2[b * SMAX + i] = clip_state_val(ps2[i], dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x[b * SMAX + i] = clip_state_val(w.s[i], dv.clip_state, dv.smin[i], dv.smax[i]);
+                L.x2[b * SMAX + i] = clip_state_val(w.s2[i], dv.clip_state, dv.smin[i], dv.smax[i]);
             }
 #pragma unroll
-            for (int j = 0; j < AD; j++) L.a[b * AD + j] = pa[j];
+            for (int j = 0; j < AD; j++) L.a[b * AD + j] = w.a[j];
         }
         __syncthreads();
 

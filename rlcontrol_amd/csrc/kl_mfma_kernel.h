@@ -334,38 +334,23 @@ __global__ __launch_bounds__(kThreads) void rlc_kl_update_mfma_kernel(RlcSacDev 
         }
         // ================= sample + gather =================
         const RlcRingMeta ring = dv.rep.ring[agent];
-        if (source == RLC_SRC_REPLAY_DEVICE_SAMPLER) {
-            const unsigned long long call = dv.rep.sample_ctr[agent];
-            __syncthreads();
-            rlc_sample_distinct(ring.size, B, dv.rep.seed[agent], call, L.pool, L.idx, L.dups);
-            if (tid == 0) dv.rep.sample_ctr[agent] = call + 1;
-        } else if (source == RLC_SRC_REPLAY_HOST_INDICES) {
-            for (int b = tid; b < B; b += kThreads) L.idx[b] = host_idx[((size_t)rel_agent * n_updates + upd) * B + b];
-        }
-        __syncthreads();
+        rlc_pick_indices<kThreads>(dv.rep, agent, ring, source, B, host_idx, (size_t)rel_agent * n_updates + upd, L.pool,
+                                   L.idx, L.dups);
         const unsigned long long nctr = dv.noise_ctr[agent];
         const int step = dv.kl_step[agent] + 1;
         for (int b = tid; b < B; b += kThreads) {
-            const float *ps, *pa, *ps2;
-            if (source == RLC_SRC_STAGING) {
-                const size_t slot = (size_t)agent * RLC_MAX_BATCH + b;
-                ps = dv.rep.gs + slot * S; pa = dv.rep.ga + slot * AD; ps2 = dv.rep.gs2 + slot * S;
-                L.r[b] = (float)dv.rep.gr[slot]; L.g[b] = (float)dv.rep.gg[slot];
-            } else {
-                const size_t slot = (size_t)agent * dv.rep.cap + ring_slot(ring, dv.rep.cap, L.idx[b]);
-                ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot * AD; ps2 = dv.rep.rs2 + slot * S;
-                L.r[b] = (float)dv.rep.rr[slot]; L.g[b] = (float)dv.rep.rg[slot];
-            }
+            const RlcRow w = rlc_locate_row(dv.rep, agent, ring, source, S, AD, b, L.idx);
+            L.r[b] = (float)w.r; L.g[b] = (float)w.g;
             for (int i = 0; i < S; i++) {
-                const float sv = ps[i];
+                const float sv = w.s[i];
                 L.x[b * SMAX + i] = sv; L.xq[b * SMAX + i] = sv; L.xn[b * SMAX + i] = sv;
-                L.x2[b * SMAX + i] = ps2[i];
+                L.x2[b * SMAX + i] = w.s2[i];
             }
 #pragma unroll
             for (int j = 0; j < AD; j++) {
                 const int at = b * AD + j;
-                L.a[at] = pa[j];
-                L.xq[b * SMAX + S + j] = pa[j];
+                L.a[at] = w.a[j];
+                L.xq[b * SMAX + S + j] = w.a[j];
                 float e;
                 if (eps_in) {
                     e = eps_in[((size_t)rel_agent * n_updates + upd) * B * AD + at];

@@ -535,5 +535,47 @@ __device__ inline void rlc_sample_distinct(long long n, int k, unsigned long lon
     }
 }
 
+// The minibatch front end of the fused update kernels (utils/replaybuffer.py:32-37), in two pieces; the row loop between
+// them and what it writes (which images, which stride, clipped or not) is each kernel's own.
+// 1. idx[0..k) <- k logical indices of `agent`'s ring, by the whole workgroup of kThreads threads; ends behind a barrier.
+//    Device sampler: the call number is the agent's live counter and thread 0 stores call + 1; with advance = false it
+//    is `call` and the counter stays (ddpg_split_kernel.h: every workgroup of an agent draws the same set and the launch
+//    advances the counter once, at its end).  Host indices: row `host_row` of the [..][k] table.  Staging: nothing.
+template <int kThreads, class PI, class PL>
+__device__ __forceinline__ void rlc_pick_indices(const RlcReplayDev& rp, int agent, const RlcRingMeta& ring, int source,
+                                                 int k, const long long* host_idx, size_t host_row, PI pool, PL idx,
+                                                 PI dups, bool advance = true, unsigned long long call = 0) {
+    if (source == RLC_SRC_REPLAY_DEVICE_SAMPLER) {
+        if (advance) call = rp.sample_ctr[agent];
+        __syncthreads();
+        rlc_sample_distinct(ring.size, k, rp.seed[agent], call, pool, idx, dups);
+        if (advance && threadIdx.x == 0) rp.sample_ctr[agent] = call + 1;
+    } else if (source == RLC_SRC_REPLAY_HOST_INDICES) {
+        for (int i = threadIdx.x; i < k; i += kThreads) idx[i] = host_idx[host_row * k + i];
+    }
+    __syncthreads();
+}
+
+// 2. row b of the minibatch: the staging slot b, or the ring slot of logical index idx[b] (idx is not read under staging)
+struct RlcRow {
+    const float *s, *a, *s2;
+    double r, g;
+};
+template <class PL>
+__device__ __forceinline__ RlcRow rlc_locate_row(const RlcReplayDev& rp, int agent, const RlcRingMeta& ring, int source,
+                                                 int S, int A, int b, PL idx) {
+    RlcRow w;
+    if (source == RLC_SRC_STAGING) {
+        const size_t slot = (size_t)agent * RLC_MAX_BATCH + b;
+        w.s = rp.gs + slot * S; w.a = rp.ga + slot * A; w.s2 = rp.gs2 + slot * S;
+        w.r = rp.gr[slot]; w.g = rp.gg[slot];
+    } else {
+        const size_t slot = (size_t)agent * rp.cap + ring_slot(ring, rp.cap, idx[b]);
+        w.s = rp.rs + slot * S; w.a = rp.ra + slot * A; w.s2 = rp.rs2 + slot * S;
+        w.r = rp.rr[slot]; w.g = rp.rg[slot];
+    }
+    return w;
+}
+
 
 #endif  // __HIPCC__

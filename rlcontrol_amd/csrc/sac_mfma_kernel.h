@@ -235,35 +235,20 @@ __global__ __launch_bounds__(kThreads) void rlc_sac_update_mfma_kernel(RlcSacDev
         }
         // ================= sample + gather (utils/replaybuffer.py:32-37) =================
         const RlcRingMeta ring = dv.rep.ring[agent];
-        if (source == RLC_SRC_REPLAY_DEVICE_SAMPLER) {
-            const unsigned long long call = dv.rep.sample_ctr[agent];
-            __syncthreads();
-            rlc_sample_distinct(ring.size, B, dv.rep.seed[agent], call, L.pool, L.idx, L.dups);
-            if (tid == 0) dv.rep.sample_ctr[agent] = call + 1;
-        } else if (source == RLC_SRC_REPLAY_HOST_INDICES) {
-            for (int b = tid; b < B; b += kThreads) L.idx[b] = host_idx[((size_t)blockIdx.x * n_updates + upd) * B + b];
-        }
-        __syncthreads();
+        rlc_pick_indices<kThreads>(dv.rep, agent, ring, source, B, host_idx, (size_t)blockIdx.x * n_updates + upd, L.pool,
+                                   L.idx, L.dups);
         const unsigned long long nctr = dv.noise_ctr[agent];
         for (int b = tid; b < B; b += kThreads) {
-            const float *ps, *pa, *ps2;
-            if (source == RLC_SRC_STAGING) {
-                const size_t slot = (size_t)agent * RLC_MAX_BATCH + b;
-                ps = dv.rep.gs + slot * S; pa = dv.rep.ga + slot * AD; ps2 = dv.rep.gs2 + slot * S;
-                L.r[b] = (float)dv.rep.gr[slot]; L.g[b] = (float)dv.rep.gg[slot];
-            } else {
-                const size_t slot = (size_t)agent * dv.rep.cap + ring_slot(ring, dv.rep.cap, L.idx[b]);
-                ps = dv.rep.rs + slot * S; pa = dv.rep.ra + slot * AD; ps2 = dv.rep.rs2 + slot * S;
-                L.r[b] = (float)dv.rep.rr[slot]; L.g[b] = (float)dv.rep.rg[slot];
-            }
+            const RlcRow w = rlc_locate_row(dv.rep, agent, ring, source, S, AD, b, L.idx);
+            L.r[b] = (float)w.r; L.g[b] = (float)w.g;
             for (int i = 0; i < S; i++) {
-                L.x[b * XL + i] = ps[i];
-                L.xc[b * XL + i] = rlc_clip_scalar(ps[i], dv.clip_state, dv.smin0, dv.smax0);
-                L.x2c[b * XL + i] = rlc_clip_scalar(ps2[i], dv.clip_state, dv.smin0, dv.smax0);
+                L.x[b * XL + i] = w.s[i];
+                L.xc[b * XL + i] = rlc_clip_scalar(w.s[i], dv.clip_state, dv.smin0, dv.smax0);
+                L.x2c[b * XL + i] = rlc_clip_scalar(w.s2[i], dv.clip_state, dv.smin0, dv.smax0);
             }
 #pragma unroll
             for (int j = 0; j < AD; j++) {
-                L.a[b * AD + j] = pa[j];
+                L.a[b * AD + j] = w.a[j];
                 float e;
                 if (eps_in) {
                     e = eps_in[(((size_t)blockIdx.x * n_updates + upd) * B + b) * AD + j];

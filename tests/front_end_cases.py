@@ -1,8 +1,10 @@
 """The case table of the minibatch front end: "pick B logical indices, map them through the ring, gather (s, a, r, s',
-gamma), clip the states", of which every fused update kernel carries its own copy.  One entry for each copy and for each
-form of a copy that changes its indexing or its block size, on the smallest shape the parity tests already run on that
-kernel.  Shared by tests/test_front_end_cases.py (CPU: the table can fail) and tests/test_gpu_minibatch_front_end.py
-(GPU: properties P1 to P5, every one bit-exact between two runs of the same kernel).
+gamma), clip the states", of which every fused update kernel is a call site (the shared body: rlc_common.h; the DDPG
+MFMA kernel alone keeps it typed out and is held to the same table).  One entry
+for each call site and for each form of one that changes its indexing or its block size, on the smallest shape the
+parity tests already run on that kernel.  Shared by tests/test_front_end_cases.py (CPU: the table can fail) and
+tests/test_gpu_minibatch_front_end.py (GPU: properties P1 to P5, every one bit-exact between two runs of the same kernel,
+and P6, the same run against recorded bits).
 
 What the table fixes for every entry: NA = 3 agents with their own Philox keys, initial weights and replay contents,
 K = 3 updates, two rings with cap = n (n = 3 B, the last size of the sampler's dense regime, and n = 3 B + 1, the first
@@ -25,7 +27,7 @@ def f32(x):
 
 class FrontEnd(object):
     """case: a Case of tests/optimizer_state_cases.py (or its WireFitting / OptimalQ / ActorExpert subclass);
-    copy: the source file that holds the front-end copy the case runs; form: what of that copy the case adds"""
+    copy: the kernel source file whose front-end call site the case runs; form: what of that call site the case adds"""
 
     def __init__(self, number, case, copy, form=""):
         self.number, self.case, self.copy, self.form = number, case, copy, form

@@ -1,7 +1,9 @@
 """The minibatch front end of every fused update kernel, pinned bit for bit: "pick B logical indices, map them through the
-ring, gather (s, a, r, s', gamma), clip the states".  Thirteen kernels carry a copy of it (tests/front_end_cases.py names
-them); every property below compares two runs of the SAME kernel that must see the same minibatch rows in the same order,
-so every assertion is np.array_equal and no tolerance appears anywhere.
+ring, gather (s, a, r, s', gamma), clip the states".  Picking the indices and locating a row are one shared body in
+rlc_common.h; twelve kernels are a call site of it and ddpg_mfma_kernel.h keeps the block typed out (DESIGN.md 4;
+tests/front_end_cases.py names all thirteen and holds them to the same properties).  P1 to P5 each compare two
+runs of the SAME kernel that must see the same minibatch rows in the same order, P6 compares a run with recorded bits, so
+every assertion is an equality and no tolerance appears anywhere.
 
 "State" of an agent: theta, theta_target, every Adam m / v blob of the family, the beta powers (the KL agents: the step
 counter) and the family's cheap taps of the last update.
@@ -14,8 +16,16 @@ P3  both upload routes of host indices: K' updates in one launch (more than 1024
 P4  the sample counter: K fused sampler calls leave it at K, host-index updates leave it at 0.
 P5  agents are isolated: agent i of three equals a one-agent population with its seed, rows and weights; update_batch(2)
     leaves agents 0 and 1 untouched and gives agent 2 what update(1, host_indices) on the same rows gives it.
+P6  the recorded bits: a front end that is wrong the same way in both runs of a pair passes P1 to P5, so the state of
+    P1's rotated, device-sampled run (K = 3, three agents) is hashed per agent and must equal the digest in
+    tests/golden/front_end_digests.json, recorded by tests/helpers/front_end_digests.py from the build of the commit
+    before the thirteen copies were merged.  It makes no run of its own: the lab already holds that one.
 
 The runs of one table entry are shared by the properties that need them (the module-scoped `lab`)."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -204,3 +214,34 @@ def test_p5_update_batch_touches_one_agent(lab):
             _same(before[i], after[i], "%s agent %d across update_batch(%d)" % (fe.id, i, agent))
     assert not np.array_equal(after[agent]["theta"], before[agent]["theta"])
     _same(after[agent], want, "%s agent %d: update_batch against update(1, host_indices) on the same rows" % (fe.id, agent))
+
+
+def state_digest(state):
+    """sha256 over the sorted keys of one agent's _state: for each key its name, dtype, shape and raw bytes"""
+    h = hashlib.sha256()
+    for k in sorted(state):
+        v = np.ascontiguousarray(state[k])
+        h.update(("%s|%s|%s|" % (k, v.dtype.str, v.shape)).encode())
+        h.update(v.tobytes())
+    return h.hexdigest()
+
+
+def digest_key(fe, regime, agent):
+    return "%s %s agent %d" % (fe.id, regime, agent)
+
+
+def lab_digests(lab):
+    """{digest_key: digest} of P1's rotated device-sampler run in both regimes"""
+    return {digest_key(lab.fe, regime, i): state_digest(lab.run(regime, True, "sampler")["state"][i])
+            for regime in T.REGIMES for i in range(NA)}
+
+
+@pytest.mark.parametrize("regime", T.REGIMES)
+def test_p6_state_has_the_recorded_bits(lab, golden_dir, regime):
+    fe = lab.fe
+    with open(os.path.join(golden_dir, "front_end_digests.json")) as f:     # a missing file or key fails
+        want = json.load(f)["digests"]
+    got = lab_digests(lab)
+    for i in range(NA):
+        key = digest_key(fe, regime, i)
+        assert got[key] == want[key], key
