@@ -255,12 +255,18 @@ def build(force=False, verbose=False, jobs=None):
     def compile_one(u):
         import json
         src, obj, defs = u
-        cmd = [_hipcc()] + CFLAGS + defs + ["-c", src, "-o", obj]
+        # the object and its report appear under their names only once they are whole: a build that is interrupted, or whose
+        # audit fails, leaves nothing the next build() would take for finished
+        part = obj[:-2] + ".part.o"
+        cmd = [_hipcc()] + CFLAGS + defs + ["-c", src, "-o", part]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-        with open(obj + ".usage.json", "w") as f:
-            json.dump(audit_object(obj), f)
+        report = json.dumps(audit_object(part))
+        with open(obj + ".usage.json.part", "w") as f:
+            f.write(report)
+        os.replace(obj + ".usage.json.part", obj + ".usage.json")
+        os.replace(part, obj)
 
     if todo:
         with ThreadPoolExecutor(max_workers=jobs or min(8, os.cpu_count() or 1)) as ex:
@@ -268,11 +274,14 @@ def build(force=False, verbose=False, jobs=None):
     import json
     usage = {}
     for _, obj, _ in _units():
-        if not os.path.exists(obj + ".usage.json"):          # an object of an older build
-            with open(obj + ".usage.json", "w") as f:
-                json.dump(audit_object(obj), f)
-        with open(obj + ".usage.json") as f:
-            usage[os.path.basename(obj)] = json.load(f)
+        try:
+            with open(obj + ".usage.json") as f:
+                usage[os.path.basename(obj)] = json.load(f)
+        except (OSError, ValueError):                        # an object of an older build, or a report cut short
+            usage[os.path.basename(obj)] = audit_object(obj)
+            with open(obj + ".usage.json.part", "w") as f:
+                json.dump(usage[os.path.basename(obj)], f)
+            os.replace(obj + ".usage.json.part", obj + ".usage.json")
     check_spill_policy(usage)                                # before the link: a refused build leaves no library
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + [u[1] for u in _units()]
     if verbose:

@@ -26,6 +26,7 @@ class Case(object):
     def __init__(self, dims, B, kernel, **kw):
         self.dims, self.B, self.kernel = tuple(dims), int(B), kernel
         self.split = kw.pop("split", 0)
+        self.seed = kw.pop("seed", 1)             # minibatch seed of the schedules that search for one (tests/mfma_unit_cases.py)
         self.kw = kw
         self.S, self.A = self.dims[0], self.dims[1]
 
