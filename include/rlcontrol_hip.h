@@ -560,6 +560,93 @@ int rlc_ae_get_kernel(const rlc_ae* h, int32_t* variant_in_use);
 /* 1 is accepted; anything above is refused: "ActorExpert has no latency mode" */
 int rlc_ae_set_split(rlc_ae* h, int32_t n_workgroups);
 
+
+/* ===================================== ActorCritic =================================================
+ * The Actor-Critic baseline (agents/ActorCritic.py:12-270, agents/network/ac_network.py:12-509;
+ * jsonfiles/agent/ac.json, ae_ll.json): a hydra network with a shared first layer, a one-mode Gaussian actor in
+ * pre-tanh space (mu linear, sigma = exp(-20 + 11 (tanh + 1))) and a critic Q(s,a) whose action rows enter at the
+ * second layer.  Action = tanh(mu + sigma * eps) * action_max, not clipped; greedy action = tanh(mu) * action_max.
+ * One update (ActorCritic.py:116-263): the critic's TD step with a' from the ONLINE actor on s' and the TARGET Q;
+ * num_samples raw samples per row on the weights after that step and their Q; one actor step on
+ * -(1/R) sum_j w_j logN(raw_j; mu, sigma); Polyak on everything.
+ * Parameter blob, variable creation order (ac_network.py:124-288):
+ *   W1[S][L1] b1 | Wp2[L1][La] bp2 | Wmu[La][A] bmu | Wls[La][A] bls | Wal[La][1] bal | Wq2[L1+A][Lc] bq2 | Wq3[Lc] bq3,
+ * the action rows are last in Wq2; the alpha head (Wal, bal; ac_network.py:166-172) receives no gradient and only
+ * follows Polyak.  num_modal is 1 (the assert of ac_network.py:175).
+ * blob selector: 0 theta, 1 target, 2 / 3 the actor Adam's m / v, 4 / 5 the critic Adam's m / v (both own W1, b1).
+ * Random draws: the caller's standard normals, or NULL for the device's Philox stream keyed by the agent's seed (they
+ * stand for TF's random ops behind mvn.sample, ac_network.py:221). */
+typedef rlc_handle rlc_ac;
+/* critic_update (ActorCritic.py:123-146): 'mean' the greedy action, 'sampled' one draw per row, 'expected' num_samples
+ * draws per row with the target Q averaged over them; 'random_q' (:148-158) is not implemented */
+enum { RLC_AC_CRITIC_UPDATE_MEAN = 0, RLC_AC_CRITIC_UPDATE_SAMPLED = 1, RLC_AC_CRITIC_UPDATE_EXPECTED = 2 };
+/* actor_update (ActorCritic.py:203-254): 'll' sample 0 weighted by q_0 - mean q, 'll_update_all' every sample weighted
+ * by q_j - mean q, 'cem' the top_k samples by Q with weight 1; 'reparam' (:256-257) is not implemented */
+enum { RLC_AC_ACTOR_UPDATE_LL = 0, RLC_AC_ACTOR_UPDATE_LL_ALL = 1, RLC_AC_ACTOR_UPDATE_CEM = 2 };
+typedef struct rlc_ac_config {
+    int32_t device, n_agents, state_dim, action_dim;    /* action_dim <= 6 */
+    int32_t shared_l1_dim, actor_l2_dim, critic_l2_dim; /* jsonfiles/agent/ac.json */
+    int32_t num_samples;                                 /* 1 .. 1024 */
+    int32_t top_k;                                       /* int(num_samples * rho), formed by the caller (ActorCritic.py:248);
+                                                            read for cem only: 1 .. num_samples */
+    int32_t critic_update, actor_update;                 /* the enums above */
+    int32_t batch_size, clip_state;                      /* clip_state: norm_type != 'none' (ac_network.py:115-118) */
+    int64_t buffer_size;
+    float tau;
+    int32_t norm_type;           /* RLC_NORM_NONE ('none' / 'input_norm') only: 'layer' and 'batch' are refused */
+    const float* state_min;      /* [state_dim] */
+    const float* state_max;
+    const float* action_max;     /* [action_dim]: the scale of the squashed action per dimension (ac_network.py:236-237) */
+    const float* actor_lr;       /* [n_agents] (ac_network.py:97-101) */
+    const float* critic_lr;      /* [n_agents] (ac_network.py:92) */
+    const uint64_t* seed;        /* [n_agents] Philox keys: the device sampler and the device's draws */
+} rlc_ac_config;
+
+/* ActorCritic_Network.__init__ + init_target_network (ac_network.py:13-105, :474-475) for every agent */
+int rlc_ac_create(const rlc_ac_config* cfg, rlc_ac** out);
+/* the length of self.net_params flattened (ac_network.py:62) */
+int rlc_ac_param_count(const rlc_ac* h, int64_t* out_p);
+/* assignment to / fetch of net_params, target_net_params (ac_network.py:62-66) and the two AdamOptimizers' slots (:92-101) */
+int rlc_ac_set_blob(rlc_ac* h, int32_t agent, int32_t which, const float* src, int64_t n);
+int rlc_ac_get_blob(rlc_ac* h, int32_t agent, int32_t which, float* dst, int64_t n);
+/* {actor beta1^t, actor beta2^t, critic beta1^t, critic beta2^t}: the AdamOptimizers' power accumulators (:92-101) */
+int rlc_ac_set_beta_powers(rlc_ac* h, int32_t agent, const float* pw4);
+int rlc_ac_get_beta_powers(rlc_ac* h, int32_t agent, float* pw4);
+/* init_target_network (ac_network.py:474-475) */
+int rlc_ac_init_target(rlc_ac* h, int32_t agent);
+/* sample 0: predict_action (ac_network.py:449-472), tanh(mu) * action_max; sample 1: one draw of sample_action
+ * (:425-443, is_single_sample), from eps [n][A] or (NULL) the device's stream (ActorCritic.py:49-114) */
+int rlc_ac_act(rlc_ac* h, int32_t first_agent, int32_t n, const double* states, int32_t sample, const float* eps,
+               float* out_actions);
+/* queued / fetched as rlc_ddpg_act_queue / rlc_ddpg_act_fetch (the take_action of the step after an update) */
+int rlc_ac_act_queue(rlc_ac* h, int32_t first_agent, int32_t n, const double* states, int32_t sample, const float* eps);
+int rlc_ac_act_fetch(rlc_ac* h, int32_t first_agent, int32_t n, float* out_actions);
+/* BaseAgent.learn for every agent: sample_batch + ActorCritic_Network_Manager.update_network (ActorCritic.py:116-263).
+ * eps_next [n_agents][n_updates][batch][n_next][action_dim] with n_next = 0 (mean: pass NULL), 1 (sampled) or
+ * num_samples (expected); eps [n_agents][n_updates][batch][num_samples][action_dim]; or both NULL */
+int rlc_ac_update(rlc_ac* h, int32_t n_updates, const int64_t* host_indices, const float* eps_next, const float* eps);
+/* update_network on the caller's minibatch; eps_next [batch][n_next][action_dim], eps [batch][num_samples][action_dim],
+ * or both NULL */
+int rlc_ac_update_batch(rlc_ac* h, int32_t agent, int32_t batch, const double* states, const double* actions,
+                        const double* next_states, const double* rewards, const double* gammas, const float* eps_next,
+                        const float* eps);
+/* taps of the last update (the values ActorCritic.py:116-263 holds in its locals): 0 Q(s,a) (predicted_q_val, :169),
+ * 1 TD target y_i (:167) (n = batch); 2 the next actions (n = batch * max(n_next, 1) * action_dim); 3 the raw samples,
+ * 4 the squashed samples (:174; n = batch * num_samples * action_dim each); 5 their Q (:189), 6 the per-sample weights
+ * w of the actor loss (cem: 1 on the selected set, 0 elsewhere) (n = batch * num_samples each); 7 the actor's gradient
+ * blob, 8 the critic's (n = P each; elements the optimizer does not own are zero) */
+int rlc_ac_last_tap(rlc_ac* h, int32_t agent, int32_t which, float* dst, int64_t n);
+/* allocate / drop taps 7 and 8 (test instrumentation; no counterpart in the reference) */
+int rlc_ac_enable_grad_taps(rlc_ac* h, int32_t on);
+/* Q(s,a) rows on one agent's online network (getQFunction, ac_network.py:480-483; predict_q, :402-408) */
+int rlc_ac_qval(rlc_ac* h, int32_t agent, int32_t n, const double* states, const double* actions, float* out_q);
+/* 0 auto and 1 generic both mean the any-shape kernel; 2 is refused: "ActorCritic runs on the any-shape kernel only"
+ * (no counterpart in the reference) */
+int rlc_ac_set_kernel(rlc_ac* h, int32_t variant);
+int rlc_ac_get_kernel(const rlc_ac* h, int32_t* variant_in_use);
+/* 1 is accepted; anything above is refused: "ActorCritic has no latency mode" (no counterpart in the reference) */
+int rlc_ac_set_split(rlc_ac* h, int32_t n_workgroups);
+
 /* ---------------------------------------------------------------------------------------------------
  * On-device experiment loop: Experiment.run of the reference
  * (experiment.py:52-217) for every agent of a DDPG population, with the environment simulated on the GPU.

@@ -43,6 +43,9 @@ EXPORTS = (
     "rlc_ae_create", "rlc_ae_param_count", "rlc_ae_set_blob", "rlc_ae_get_blob", "rlc_ae_set_beta_powers", "rlc_ae_get_beta_powers",
     "rlc_ae_init_target", "rlc_ae_act", "rlc_ae_act_queue", "rlc_ae_act_fetch", "rlc_ae_update", "rlc_ae_update_batch",
     "rlc_ae_last_tap", "rlc_ae_enable_grad_taps", "rlc_ae_qval", "rlc_ae_set_kernel", "rlc_ae_get_kernel", "rlc_ae_set_split",
+    "rlc_ac_create", "rlc_ac_param_count", "rlc_ac_set_blob", "rlc_ac_get_blob", "rlc_ac_set_beta_powers", "rlc_ac_get_beta_powers",
+    "rlc_ac_init_target", "rlc_ac_act", "rlc_ac_act_queue", "rlc_ac_act_fetch", "rlc_ac_update", "rlc_ac_update_batch",
+    "rlc_ac_last_tap", "rlc_ac_enable_grad_taps", "rlc_ac_qval", "rlc_ac_set_kernel", "rlc_ac_get_kernel", "rlc_ac_set_split",
     "rlc_ddpg_rollout_create", "rlc_ddpg_rollout_run", "rlc_sac_rollout_create", "rlc_sac_rollout_run", "rlc_kl_rollout_create", "rlc_kl_rollout_run",
     "rlc_naf_rollout_create", "rlc_naf_rollout_run", "rlc_rollout_counts", "rlc_rollout_train_log",
     "rlc_rollout_eval_log", "rlc_rollout_observation",
@@ -148,6 +151,21 @@ class rlc_ae_config(ctypes.Structure):
         ("state_min", ctypes.POINTER(ctypes.c_float)), ("state_max", ctypes.POINTER(ctypes.c_float)),
         ("action_min", ctypes.POINTER(ctypes.c_float)), ("action_max", ctypes.POINTER(ctypes.c_float)),
         ("actor_lr", ctypes.POINTER(ctypes.c_float)), ("expert_lr", ctypes.POINTER(ctypes.c_float)),
+        ("seed", ctypes.POINTER(ctypes.c_uint64)),
+    ]
+
+
+class rlc_ac_config(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("state_dim", ctypes.c_int32),
+        ("action_dim", ctypes.c_int32), ("shared_l1_dim", ctypes.c_int32), ("actor_l2_dim", ctypes.c_int32),
+        ("critic_l2_dim", ctypes.c_int32), ("num_samples", ctypes.c_int32), ("top_k", ctypes.c_int32),
+        ("critic_update", ctypes.c_int32), ("actor_update", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32), ("clip_state", ctypes.c_int32),
+        ("buffer_size", ctypes.c_int64), ("tau", ctypes.c_float), ("norm_type", ctypes.c_int32),
+        ("state_min", ctypes.POINTER(ctypes.c_float)), ("state_max", ctypes.POINTER(ctypes.c_float)),
+        ("action_max", ctypes.POINTER(ctypes.c_float)),
+        ("actor_lr", ctypes.POINTER(ctypes.c_float)), ("critic_lr", ctypes.POINTER(ctypes.c_float)),
         ("seed", ctypes.POINTER(ctypes.c_uint64)),
     ]
 

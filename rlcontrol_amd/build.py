@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 STAMPS = os.environ.get("RLC_STAMPS", "0") == "1"
 OBJ = os.path.join(CSRC, ("_obj_stamps" if STAMPS else "_obj") + ("_fast" if os.environ.get("RLC_FAST_BUILD", "0") == "1" else ""))
 OUT = os.path.join(_HERE, "librlcontrol_hip_stamps.so" if STAMPS else "librlcontrol_hip.so")
-PLAIN = ("rlc_api.hip", "rlc_api_sac.hip", "rlc_api_naf.hip", "rlc_api_optq.hip", "rlc_api_wf.hip", "rlc_api_ae.hip", "replay_kernels.hip", "ddpg_generic.hip", "ddpg_mfma.hip", "sac_generic.hip", "sac_mfma.hip", "naf_generic.hip", "naf_mfma.hip", "optq_generic.hip", "wf_generic.hip", "ae_generic.hip", "rollout_kernels.hip", "rlc_api_rollout.hip", "kl_generic.hip", "rlc_api_kl.hip", "ddpg_split.hip", "kl_mfma.hip", "kl_mfma_a2.hip")
+PLAIN = ("rlc_api.hip", "rlc_api_sac.hip", "rlc_api_naf.hip", "rlc_api_optq.hip", "rlc_api_wf.hip", "rlc_api_ae.hip", "rlc_api_ac.hip", "replay_kernels.hip", "ddpg_generic.hip", "ddpg_mfma.hip", "sac_generic.hip", "sac_mfma.hip", "naf_generic.hip", "naf_mfma.hip", "optq_generic.hip", "wf_generic.hip", "ae_generic.hip", "ac_generic.hip", "rollout_kernels.hip", "rlc_api_rollout.hip", "kl_generic.hip", "rlc_api_kl.hip", "ddpg_split.hip", "kl_mfma.hip", "kl_mfma_a2.hip")
 MFMA_VARIANTS = [(mt, ad) for ad in (1, 2) for mt in (2, 4, 7, 8)]
 # the wide form of the DDPG kernel (state_dim <= 32, action_dim in {1,2,3,4,6}; ddpg_mfma_kernel.h, WIDE): no tail-of-four units
 MFMA_WIDE_VARIANTS = [(mt, ad) for ad in (1, 2, 3, 4, 6) for mt in (2, 4, 7, 8)]
@@ -92,7 +92,7 @@ def _units():
 _LLVM = "/opt/rocm/lib/llvm/bin"
 # Units whose kernels must not carry whole-wave spills (see audit_object); the MFMA kernels are reported, not refused:
 # their SGPR spills sit at phase boundaries and they run two waves per SIMD with the full 256-register budget.
-GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o", "optq_generic.o", "wf_generic.o", "ae_generic.o") + tuple(
+GUARDED_UNITS = ("ddpg_generic.o", "sac_generic.o", "naf_generic.o", "kl_generic.o", "optq_generic.o", "wf_generic.o", "ae_generic.o", "ac_generic.o") + tuple(
     "ddpg_mfma_w_%d_%d.o" % v for v in MFMA_WIDE_VARIANTS) + tuple(     # the wide DDPG, SAC and NAF units are held to the same policy
     "ddpg_mfma_ln_%d_%d.o" % v for v in MFMA_LN_VARIANTS) + tuple(      # ... and the layer-norm DDPG units
     "sac_mfma_w_%d_%d_%d.o" % v for v in SAC_WIDE_VARIANTS) + tuple(

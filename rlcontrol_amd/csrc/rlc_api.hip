@@ -181,6 +181,7 @@ int rlc_h_init_common(rlc_handle* h, int algo, int device, int n_agents, int S, 
     memset(&h->optq, 0, sizeof(h->optq));
     memset(&h->wf, 0, sizeof(h->wf));
     memset(&h->ae, 0, sizeof(h->ae));
+    memset(&h->ac, 0, sizeof(h->ac));
     RLC_HIP(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
     (void)hipEventCreate(&h->ev0);
     (void)hipEventCreate(&h->ev1);
@@ -335,7 +336,7 @@ int rlc_h_last_tap(rlc_handle* h, int algo, int agent, int which, float* dst, in
         const RlcTap t = rlc_tap(dv, which, h->B);
         RLC_REQUIRE(t.base, "tap %d not available (gradient taps need %s_enable_grad_taps)", which,
                     algo == RLC_ALGO_DDPG ? "rlc_ddpg" : algo == RLC_ALGO_NAF ? "rlc_naf" : algo == RLC_ALGO_OPTQ ? "rlc_optq"
-                    : algo == RLC_ALGO_WF ? "rlc_wf" : algo == RLC_ALGO_AE ? "rlc_ae" : "*");
+                    : algo == RLC_ALGO_WF ? "rlc_wf" : algo == RLC_ALGO_AE ? "rlc_ae" : algo == RLC_ALGO_AC ? "rlc_ac" : "*");
         RLC_REQUIRE(n == t.len, "tap %d holds %lld floats, caller asked for %lld", which, t.len, (long long)n);
         const float* src = t.base + (size_t)agent * t.stride;
         if (t.blob) return fetch_blob(h, dv.d, src, dst);     // gradient blobs use the padded device layout

@@ -12,10 +12,11 @@
 #include "optq_common.h"
 #include "wf_common.h"
 #include "ae_common.h"
+#include "ac_common.h"
 
 // KL: ReverseKL / ForwardKL, on RlcSacDev
 enum RlcAlgo { RLC_ALGO_DDPG = 1, RLC_ALGO_SAC = 2, RLC_ALGO_NAF = 3, RLC_ALGO_KL = 4, RLC_ALGO_OPTQ = 5, RLC_ALGO_WF = 6,
-               RLC_ALGO_AE = 7 };
+               RLC_ALGO_AE = 7, RLC_ALGO_AC = 8 };
 
 struct rlc_handle {
     int algo;
@@ -56,6 +57,8 @@ struct rlc_handle {
     RlcWfDev wf;
     // ---- ActorExpert
     RlcAeDev ae;
+    // ---- ActorCritic
+    RlcAcDev ac;
     // ---- on-device experiment loop (rlc_api_rollout.hip)
     bool has_env;
     RlcEnvDev env;
@@ -78,7 +81,7 @@ int rlc_h_split_after_launch(rlc_handle* h);
 inline const char* rlc_algo_name(int algo) {
     return algo == RLC_ALGO_DDPG ? "DDPG" : algo == RLC_ALGO_SAC ? "SoftActorCritic" : algo == RLC_ALGO_NAF ? "NAF"
            : algo == RLC_ALGO_OPTQ ? "OptimalQ" : algo == RLC_ALGO_WF ? "WireFitting"
-           : algo == RLC_ALGO_AE ? "ActorExpert" : "ReverseKL / ForwardKL";
+           : algo == RLC_ALGO_AE ? "ActorExpert" : algo == RLC_ALGO_AC ? "ActorCritic" : "ReverseKL / ForwardKL";
 }
 #define RLC_NEED(h, a) RLC_REQUIRE((h) && (h)->algo == (a), "handle is not a %s population", rlc_algo_name(a))
 
@@ -86,7 +89,8 @@ inline const char* rlc_algo_name(int algo) {
 template <class F>
 int rlc_h_with_dev(rlc_handle* h, F f) {
     return h->algo == RLC_ALGO_DDPG ? f(h->dv) : h->algo == RLC_ALGO_NAF ? f(h->naf) : h->algo == RLC_ALGO_OPTQ ? f(h->optq)
-           : h->algo == RLC_ALGO_WF ? f(h->wf) : h->algo == RLC_ALGO_AE ? f(h->ae) : f(h->sac);
+           : h->algo == RLC_ALGO_WF ? f(h->wf) : h->algo == RLC_ALGO_AE ? f(h->ae) : h->algo == RLC_ALGO_AC ? f(h->ac)
+           : f(h->sac);
 }
 
 // the per-agent parameter-shaped blobs [n_agents][Ppad], in the order of the ABI's blob selector
@@ -96,6 +100,7 @@ inline std::vector<float**> rlc_blobs(RlcNafDev& v) { return {&v.theta, &v.theta
 inline std::vector<float**> rlc_blobs(RlcOptqDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
 inline std::vector<float**> rlc_blobs(RlcWfDev& v) { return {&v.theta, &v.theta_t, &v.m, &v.v}; }
 inline std::vector<float**> rlc_blobs(RlcAeDev& v) { return {&v.theta, &v.theta_t, &v.m_a, &v.v_a, &v.m_c, &v.v_c}; }
+inline std::vector<float**> rlc_blobs(RlcAcDev& v) { return {&v.theta, &v.theta_t, &v.m_a, &v.v_a, &v.m_c, &v.v_c}; }
 // the gradient taps, blobs that exist only after *_enable_grad_taps
 inline std::vector<float**> rlc_grad_taps(RlcDev& v) { return {&v.tap_gc, &v.tap_ga}; }
 inline std::vector<float**> rlc_grad_taps(RlcSacDev& v) { return {&v.tap_g}; }
@@ -103,6 +108,7 @@ inline std::vector<float**> rlc_grad_taps(RlcNafDev& v) { return {&v.tap_g}; }
 inline std::vector<float**> rlc_grad_taps(RlcOptqDev& v) { return {&v.tap_g}; }
 inline std::vector<float**> rlc_grad_taps(RlcWfDev& v) { return {&v.tap_g}; }
 inline std::vector<float**> rlc_grad_taps(RlcAeDev& v) { return {&v.tap_ga, &v.tap_gc}; }
+inline std::vector<float**> rlc_grad_taps(RlcAcDev& v) { return {&v.tap_ga, &v.tap_gc}; }
 // the same dims with the other weight layout
 inline RlcDims rlc_with_layout(const RlcDims& d, int blocked) {
     return rlc_make_dims(d.S, d.A, d.H1, d.HA, d.HC, d.B, blocked, d.norm, d.sep);
@@ -116,12 +122,14 @@ inline RlcNafDims rlc_with_layout(const RlcNafDims& d, int blocked) {
 inline RlcOptqDims rlc_with_layout(const RlcOptqDims& d, int) { return d; }     // one layout: row-major
 inline RlcWfDims rlc_with_layout(const RlcWfDims& d, int) { return d; }         // one layout: row-major
 inline RlcAeDims rlc_with_layout(const RlcAeDims& d, int) { return d; }         // one layout: row-major
+inline RlcAcDims rlc_with_layout(const RlcAcDims& d, int) { return d; }         // one layout: row-major
 inline int rlc_beta_powers(const RlcDev&) { return 4; }
 inline int rlc_beta_powers(const RlcSacDev&) { return 4; }
 inline int rlc_beta_powers(const RlcNafDev&) { return 2; }
 inline int rlc_beta_powers(const RlcOptqDev&) { return 2; }
 inline int rlc_beta_powers(const RlcWfDev&) { return 2; }
 inline int rlc_beta_powers(const RlcAeDev&) { return 4; }
+inline int rlc_beta_powers(const RlcAcDev&) { return 4; }
 // tap `which` of the last update: all agents' array (null: not available), per-agent stride, floats the caller gets,
 // blob = stored in the padded device layout of a parameter blob
 struct RlcTap { const float* base; size_t stride; long long len; bool blob; };
@@ -177,6 +185,20 @@ inline RlcTap rlc_tap(const RlcAeDev& v, int which, int B) {
                         {v.tap_gc, (size_t)v.d.Ppad, v.d.P, true}};
     return which >= 0 && which < 9 ? t[which] : RlcTap{nullptr, 0, 0, false};
 }
+inline RlcTap rlc_tap(const RlcAcDev& v, int which, int B) {
+    const size_t MB = RLC_MAX_BATCH, A = v.d.A, SN = (size_t)B * v.d.n;
+    const size_t NX = (size_t)B * rlc_ac_next_actions(v.critic_mode, v.d.n) * A;
+    const RlcTap t[] = {{v.tap_q, MB, B, false},
+                        {v.tap_y, MB, B, false},
+                        {v.tap_anext, NX, (long long)NX, false},
+                        {v.tap_raw, SN * A, (long long)(SN * A), false},
+                        {v.tap_sa, SN * A, (long long)(SN * A), false},
+                        {v.tap_sq, SN, (long long)SN, false},
+                        {v.tap_w, SN, (long long)SN, false},
+                        {v.tap_ga, (size_t)v.d.Ppad, v.d.P, true},
+                        {v.tap_gc, (size_t)v.d.Ppad, v.d.P, true}};
+    return which >= 0 && which < 9 ? t[which] : RlcTap{nullptr, 0, 0, false};
+}
 // kernel variant in use (1 generic, 2 mfma): the request h->variant (0 auto) resolved against the shape support
 inline int rlc_h_variant(const rlc_handle* h) {
     if (h->variant == 1 || h->variant == 2) return h->variant;
@@ -187,6 +209,7 @@ inline int rlc_h_variant(const rlc_handle* h) {
         case RLC_ALGO_OPTQ: return 1;     // the any-shape kernel only
         case RLC_ALGO_WF: return 1;       // the any-shape kernel only
         case RLC_ALGO_AE: return 1;       // the any-shape kernel only
+        case RLC_ALGO_AC: return 1;       // the any-shape kernel only
         // above one action dimension the KL MFMA kernel is opt-in (rlc_kl_set_kernel)
         default: return (h->sac.d.A == 1 && rlc_kl_mfma_supported(h->sac.d, h->sac.kl_nodes)) ? 2 : 1;
     }

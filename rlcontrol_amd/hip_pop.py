@@ -3,7 +3,7 @@ has under its own symbol prefix (blobs, taps, update, queued acting, kernel choi
 
 One handle = a population of independent agents of ONE algorithm on one MI355X (include/rlcontrol_hip.h).
 The per-algorithm classes (hip_ddpg.DDPGPopulation, hip_sac.SACPopulation, hip_naf.NAFPopulation, hip_kl.KLPopulation,
-hip_optq.OptQPopulation, hip_wf.WFPopulation, hip_ae.AEPopulation) add the constructor, the tables (PREFIX, BLOB, TAP, BETA_POWERS, tap_lengths) and what only they have."""
+hip_optq.OptQPopulation, hip_wf.WFPopulation, hip_ae.AEPopulation, hip_ac.ACPopulation) add the constructor, the tables (PREFIX, BLOB, TAP, BETA_POWERS, tap_lengths) and what only they have."""
 import ctypes
 from collections import OrderedDict
 

@@ -17,6 +17,7 @@ _AGENTS = {
     "OptimalQ": ("rlcontrol_amd.agents.OptimalQ", "OptimalQ"),
     "WireFitting": ("rlcontrol_amd.agents.WireFitting", "WireFitting"),
     "ActorExpert": ("rlcontrol_amd.agents.ActorExpert", "ActorExpert"),
+    "ActorCritic": ("rlcontrol_amd.agents.ActorCritic", "ActorCritic"),
 }
 
 
